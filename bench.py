@@ -9,10 +9,18 @@ data-path collective in the timed steps); the rendered RGB-D-N images are collec
 ("final image collection"), executed once after the timed steps and timed on its own, and once
 inside the timed cascaded sample of every rank.
 
-The timed region holds the K forwards (and, for N > 1, the gather) only; stage events, the parity check, the CPU baseline
-and the denoiser / cascade sections run afterwards, untimed.
+The timed region holds the K forwards only.  A plain run does nothing else: it sets up, warms up, times the K forwards, writes
+the outputs of the last one (--dump-outputs DIR) and prints the JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the configuration).  Everything below runs afterwards, untimed, with --full only (the --no-* switches leave parts
+of it out): stage events and the roofline, the stress scene and two streams, the parity check, the CPU baseline, the denoiser /
+conditioner / decode sections, the backward and mesh export, the cascade, and for N > 1 the timed gather.
 
-Also on the JSON line:
+--dump-outputs DIR: what the timed forward hands its caller after the last timed step -- DIR/color.npy [V,3,H,W],
+DIR/radii.npy [V,N] (as float32) and DIR/allmap.npy [V,7,H,W] -- in float32, at most 64 MB in all: an array that does not fit
+its share is written as DIR/<name>_sample.npy, the elements at a fixed seeded sample of flat indices (sorted).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
+
+Also on the JSON line of a --full run:
   parity       -- the bench workload itself, HIP path vs oracle, every view (bit-identical bins, pixel MSE <= 1e-5).
   sec_per_sample / cascade -- BASELINE configs[3]/[4]: one 250-step cascaded sample per GPU (stage-1 DiT-L, stage-2 DiT-L,
                   surfel decode, renders), all ranks, one gather to rank 0; euler (249 NFE per stage) and, at N=1, dopri5.
@@ -721,6 +729,31 @@ def summary_of(out):
     return sm
 
 
+DUMP_BUDGET_BYTES = 64 * 10 ** 6 - 4096   # all .npy files of --dump-outputs together, headers included
+
+
+def dump_outputs(path, plan):
+    """--dump-outputs: the arrays of the last forward as float32 .npy files in `path`, smallest first, each in full while it fits
+    an even share of what is left of the budget, else a fixed seeded sample of its elements (<name>_sample.npy)."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = [(name, t.cpu().numpy().astype(np.float32, copy=False)) for name, t in
+              (("color", plan.color), ("radii", plan.radii), ("allmap", plan.allmap))]
+    arrays.sort(key=lambda na: na[1].nbytes)
+    left = DUMP_BUDGET_BYTES
+    for i, (name, a) in enumerate(arrays):
+        share = left // (len(arrays) - i)
+        if a.nbytes <= share:
+            fname, data = f"{name}.npy", a
+        else:
+            k = share // a.itemsize
+            idx = np.sort(np.random.default_rng(20251016).choice(a.size, size=k, replace=False))
+            fname, data = f"{name}_sample.npy", a.reshape(-1)[idx]
+            print(f"bench.py: {name} {list(a.shape)} is written as {k} of its {a.size} elements at seeded sample indices", file=sys.stderr)
+        np.save(os.path.join(path, fname), data)
+        left -= data.nbytes
+
+
 def self_launch(n, argv):
     """Re-execute this script as `n` ranks of one node: python -m torch.distributed.run --nnodes=1 --nproc-per-node n ...
     (rank 0 prints the JSON line on the inherited stdout).  Returns the launcher's exit code."""
@@ -745,6 +778,12 @@ def main():
     ap.add_argument("--points", type=int, default=100_000)
     ap.add_argument("--views", type=int, default=8)
     ap.add_argument("--size", type=int, default=512)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every untimed section of the report (stage events, roofline, parity, CPU "
+                         "baseline, denoisers, decode, conditioner, backward, mesh export, cascade, gather); the --no-* switches "
+                         "leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed forward to DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stage-events", action="store_true")
     ap.add_argument("--no-parity", action="store_true", help="skip the untimed HIP-vs-oracle check of the bench workload")
@@ -757,6 +796,8 @@ def main():
                          "(~40 s) and compare; off by default: tests/test_dit_gpu.py asserts the same quantity and "
                          "profiles/r6_traj250.txt holds the 250-point run")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks here (one process per GPU through torch.distributed.run,
@@ -809,7 +850,7 @@ def main():
     plan.ensure_capacity()
     gathered = None
     payload = None
-    if dist is not None:
+    if dist is not None and a.full:
         payload = torch.empty((a.views, 10, H, W), dtype=torch.float32, device=dev)
         gathered = torch.empty((world, a.views, 10, H, W), dtype=torch.float32, device=dev) if rank == 0 else None
 
@@ -832,11 +873,13 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, plan)
     # the one exchange of the multi-GPU layout -- the rendered views of every rank collected on rank 0 -- is not a step of
     # the rasterizer: it is executed once here and timed on its own (the cascade section below times it where it belongs,
     # at the end of a whole sample)
     gather_ms = None
-    if dist is not None:
+    if dist is not None and a.full:
         torch.cuda.synchronize()
         dist.barrier()
         tg = time.perf_counter()
@@ -851,7 +894,7 @@ def main():
 
     # ---- untimed: per-stage durations from HIP events on the launch stream (a separate pass of the same forwards) -------
     stage = total_dev = None
-    if rank == 0 and not a.no_stage_events:
+    if rank == 0 and a.full and not a.no_stage_events:
         nev = min(a.steps, 30)
         ev = [HipEvents(5) for _ in range(nev)]
         for k in range(nev):
@@ -877,8 +920,8 @@ def main():
                                    f"views, forward raster, 1 sample per GPU",
                        "scene": a.scene, "points": n, "views": v, "image": [H, W], "num_rendered_D": int(st[0]),
                        "longest_tile_list": int(st[2]),
-                       "multi_gpu": "independent samples per rank, no collective in the timed steps; the one RCCL gather of "
-                                    "[V,10,H,W] fp32 per rank to rank 0 runs once after them (gather_ms) and inside the "
+                       "multi_gpu": "independent samples per rank, no collective in the timed steps; with --full the one RCCL gather "
+                                    "of [V,10,H,W] fp32 per rank to rank 0 runs once after them (gather_ms) and inside the "
                                     "timed cascade sample" if world > 1 else "single GPU",
                        "gather_ms": None if gather_ms is None else round(gather_ms, 3)},
         }
@@ -961,20 +1004,20 @@ def main():
                 out["two_streams"] = {"ms_per_pair_of_forwards": round(pms, 4), "Msplats_per_s": round(2 * n * v / pms / 1e3, 1),
                                       "note": "two independent 100k-surfel sets x 8 views on two streams, NOT the headline (one forward at a time)"}
                 del plan2
-        if not a.no_parity:
+        if a.full and not a.no_parity:
             out["parity"] = parity_check(g, cams, H, W, dev)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(g, cams, H, W)
-        if world == 1 and not a.no_dit and not a.no_parity and not a.trajectory_parity:
+        if a.full and world == 1 and not a.no_dit and not a.no_parity and not a.trajectory_parity:
             ev = traj250_evidence()     # the committed full-length run (tools/parity_r6.py traj250 on a GPU box), quoted -- not measured in this run
             if ev is not None:
                 out.setdefault("parity", {})["trajectory_250_points"] = ev
-        if world == 1 and not a.no_dit and not a.no_parity and a.trajectory_parity:
+        if a.full and world == 1 and not a.no_dit and not a.no_parity and a.trajectory_parity:
             tp = trajectory_parity(dev)     # BASELINE configs[2] at real depth against the fp32 oracle trajectory (CPU: ~40 s)
             out.setdefault("parity", {})["trajectory"] = tp
             out["parity"]["trajectory_rel_l2"] = tp["trajectory_rel_l2"]
             out["parity"]["pass"] = bool(out["parity"].get("pass", True) and tp["pass"])
-        if world == 1 and not a.no_dit:
+        if a.full and world == 1 and not a.no_dit:
             # second half of the headline metric ("sec/sample 250-step cascaded"): the two release-size denoisers
             out["dit"] = [bench_dit(dev, arch, a.dit_nfe, 3, parity_mode=(arch == "DiT-PixArt-PCD-CLAY-B")) for arch in
                           ("DiT-PixArt-PCD-CLAY-B", "DiT-PixArt-PCD-CLAY-L", "DiT-PixArt-PCD-CLAY-stage2-L")]
@@ -995,11 +1038,11 @@ def main():
                                                                 if gj else None)
             out["decode"] = bench_decode(dev, cams)
             out["conditioner"] = bench_conditioner(dev)
-        if world == 1 and not a.no_extras and not a.no_dit:   # (--no-dit is the quick rasterizer-only mode of the tools)
+        if a.full and world == 1 and not a.no_extras and not a.no_dit:   # (--no-dit is the quick rasterizer-only mode of the tools)
             out["backward"] = bench_backward(m, o, c, s, r, cams, H, W, dev)
             out["mesh_export"] = bench_mesh_export(g, cams, dev)
     # ---- BASELINE configs[3] / [4]: one cascaded sample per GPU, every rank takes part -------------------------------
-    if not a.no_dit and not a.no_cascade:
+    if a.full and not a.no_dit and not a.no_cascade:
         del plan
         torch.cuda.empty_cache()
         casc = bench_cascade(dev, cams, rank, world, dist)

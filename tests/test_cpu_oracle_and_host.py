@@ -288,70 +288,127 @@ def test_odeint_matches_oracle_and_analytic(method):
         assert s1["nfe"] == len(t) - 1                       # "250 steps" = 249 function evaluations
 
 
-def _reference_transport():
-    """the reference's transport package, imported with the oracle integrator standing in for torchdiffeq"""
+def _standin_transport():
+    """A stand-in of the reference's transport package with the interface ``bind_reference_transport`` patches: ``integrators.ode``
+    (drift, t, sampler_type, atol, rtol; ``sample`` integrates through an odeint -- here the oracle integrator, where the reference
+    calls torchdiffeq) and the probability-flow drift ``body_fn`` closing over ``velocity_ode`` / ``score_ode`` / ``noise_ode``
+    (transport/transport.py:193-225), with the coefficients of the three path plans (transport/path.py) and the sampling intervals
+    (transport/__init__.py, check_interval) restated.  tests/golden/transport_ref.pt holds the reference's own results
+    (tests/golden/make_transport_golden.py) that it must reproduce."""
+    import math
     import types
     from oracle import ode as oo
-    ref_root = "/root/reference"
-    if not os.path.isdir(ref_root):
-        pytest.skip("reference tree not present (GPU box)")
 
-    def fake_odeint(fn, x, t, method, atol, rtol):
-        return torch.from_numpy(oo.odeint(lambda ts, y: fn(torch.tensor(ts, dtype=torch.float32),
-                                                            torch.from_numpy(y).float()).numpy(),
-                                          x.numpy(), t.numpy(), method=method, atol=atol[0], rtol=rtol[0])).float()
+    def expand(t, x):
+        return t.view(t.size(0), *([1] * (x.dim() - 1)))
 
-    saved = {k: sys.modules.get(k) for k in ("torchdiffeq", "sgm", "sgm.util", "transport")}
-    sys.modules["torchdiffeq"] = types.SimpleNamespace(odeint=fake_odeint)
-    sys.modules["sgm"] = types.ModuleType("sgm")
-    sys.modules["sgm.util"] = types.SimpleNamespace(instantiate_from_config=lambda *a, **k: None)
-    sys.path.insert(0, ref_root)
-    for k in [k for k in sys.modules if k == "transport" or k.startswith("transport.")]:
-        del sys.modules[k]
-    import transport as ref_transport
+    def linear(t):            # sigma_t, d sigma_t / dt, d alpha_t / dt / alpha_t
+        return 1 - t, -1, 1 / t
 
-    def restore():
-        sys.path.remove(ref_root)
-        for k in [k for k in sys.modules if k == "transport" or k.startswith("transport.")]:
-            del sys.modules[k]
-        for k, v in saved.items():
-            if v is not None:
-                sys.modules[k] = v
-            else:
-                sys.modules.pop(k, None)
-    return ref_transport, restore
+    def gvp(t):
+        return torch.cos(t * math.pi / 2), -math.pi / 2 * torch.sin(t * math.pi / 2), math.pi / (2 * torch.tan(t * math.pi / 2))
+
+    def vp_sigma(t, smin=0.1, smax=20.0):
+        return torch.sqrt(1 - torch.exp(2 * (-0.25 * ((1 - t) ** 2) * (smax - smin) - 0.5 * (1 - t) * smin)))
+
+    def drift_terms(path_type, x, t):
+        """(drift mean, drift variance) of the probability-flow ODE in score form, and sigma_t"""
+        t = expand(t, x)
+        if path_type == "VP":
+            beta = 0.1 + (1 - t) * (20.0 - 0.1)
+            return -0.5 * beta * x, beta / 2, vp_sigma(t)
+        sigma, d_sigma, ratio = (linear if path_type == "Linear" else gvp)(t)
+        return -(ratio * x), ratio * (sigma ** 2) - sigma * d_sigma, sigma
+
+    class Transport:
+        def __init__(self, path_type, prediction):
+            self.path_type, self.prediction = path_type, prediction
+            eps = 1e-3 if path_type == "VP" or prediction != "velocity" else 0.0
+            t0 = eps if path_type != "VP" and prediction != "velocity" else 0
+            self.interval = (t0, 1 - eps if eps else 1)
+
+        def get_drift(self):
+            path_type = self.path_type
+
+            def score_ode(x, t, model, **model_kwargs):
+                mean, var, _ = drift_terms(path_type, x, t)
+                return -mean + var * model(x, t, **model_kwargs)
+
+            def noise_ode(x, t, model, **model_kwargs):
+                mean, var, sigma = drift_terms(path_type, x, t)
+                return -mean + var * (model(x, t, **model_kwargs) / -sigma)
+
+            def velocity_ode(x, t, model, **model_kwargs):
+                return model(x, t, **model_kwargs)
+
+            drift_fn = {"score": score_ode, "noise": noise_ode}.get(self.prediction, velocity_ode)
+
+            def body_fn(x, t, model, **model_kwargs):
+                out = drift_fn(x, t, model, **model_kwargs)
+                assert out.shape == x.shape
+                return out
+            return body_fn
+
+    class ode:  # noqa: N801  (the reference's class name: bind_reference_transport patches ode.sample)
+        def __init__(self, drift, *, t0, t1, sampler_type, num_steps, atol, rtol):
+            self.drift, self.t, self.atol, self.rtol, self.sampler_type = drift, torch.linspace(t0, t1, num_steps), atol, rtol, sampler_type
+
+        def sample(self, x, model, **model_kwargs):
+            def fn(ts, y):
+                xx = torch.from_numpy(y).float()
+                return self.drift(xx, torch.ones(xx.size(0)) * torch.tensor(ts, dtype=torch.float32), model, **model_kwargs).numpy()
+            return torch.from_numpy(integrators.odeint(fn, x.numpy(), self.t.numpy(), method=self.sampler_type, atol=self.atol,
+                                                       rtol=self.rtol)).float()
+
+    class Sampler:
+        def __init__(self, transport):
+            self.transport = transport
+
+        def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3):
+            t0, t1 = self.transport.interval
+            return ode(self.transport.get_drift(), t0=t0, t1=t1, sampler_type=sampling_method, num_steps=num_steps, atol=atol,
+                       rtol=rtol).sample
+
+    def create_transport(path_type, prediction, *_, **__):
+        return Transport(path_type, prediction)
+
+    integrators = types.SimpleNamespace(ode=ode, odeint=oo.odeint)
+    return types.SimpleNamespace(create_transport=create_transport, Sampler=Sampler, integrators=integrators)
 
 
 @pytest.mark.parametrize("path_type", ["Linear", "GVP", "VP"])
 @pytest.mark.parametrize("prediction", ["velocity", "score", "noise"])
 def test_bound_reference_transport_integrates_with_this_package(path_type, prediction):
-    """the REFERENCE'S OWN transport package (every parametrisation, every path plan -- none of it is
-    rebuilt here) with ``bind_reference_transport`` applied keeps its results while ``ode.sample`` no longer reaches torchdiffeq:
-    euler and dopri5, state by state against the unpatched reference driven by the oracle integrator."""
+    """the reference's transport package (every parametrisation, every path plan -- none of it is
+    rebuilt in the package) with ``bind_reference_transport`` applied keeps its results while ``ode.sample`` no longer reaches its
+    odeint: euler and dopri5, state by state against the unpatched package driven by the oracle integrator.  The package is the
+    stand-in of ``_standin_transport``, whose unpatched results are first held to the reference's own (tests/golden/transport_ref.pt)."""
     from gaussiananything_amd.transport import bind_reference_transport
-    ref_transport, restore = _reference_transport()
+    ref_transport = _standin_transport()
+    golden = torch.load(synthetic.fixture_path("transport_ref.pt"))
+    model = lambda x, t, scale=1.0: torch.tanh(scale * x) * (0.5 + t.view(-1, 1, 1)) - 0.3 * x  # noqa: E731
+    x0 = torch.randn(3, 4, 2, generator=torch.Generator().manual_seed(5))
+    assert torch.equal(x0, golden["bound_x0"])
+    rt = ref_transport.create_transport(path_type, prediction, None, None, None, snr_type="uniform")
+    # (score / noise drifts are singular at an end of the interval: the adaptive controller is exercised on the velocity models)
+    methods = ("euler", "dopri5") if prediction == "velocity" else ("euler", "heun3")
+    want = {m: ref_transport.Sampler(rt).sample_ode(sampling_method=m, num_steps=9)(x0, model, scale=1.5) for m in methods}
+    for m in methods:
+        ref = golden["bound"][f"{path_type}/{prediction}"][m]
+        assert want[m].shape == ref.shape and torch.allclose(want[m], ref, rtol=1e-5, atol=1e-6, equal_nan=True), \
+            (m, float((want[m] - ref).abs().max()))
+    theirs = ref_transport.integrators.ode.sample
+    bind_reference_transport(ref_transport.integrators)
+    stand_in = ref_transport.integrators.odeint
     try:
-        model = lambda x, t, scale=1.0: torch.tanh(scale * x) * (0.5 + t.view(-1, 1, 1)) - 0.3 * x  # noqa: E731
-        x0 = torch.randn(3, 4, 2, generator=torch.Generator().manual_seed(5))
-        rt = ref_transport.create_transport(path_type, prediction, None, None, None, snr_type="uniform")
-        # (score / noise drifts are singular at an end of the interval: the adaptive controller is exercised on the velocity models)
-        methods = ("euler", "dopri5") if prediction == "velocity" else ("euler", "heun3")
-        want = {m: ref_transport.Sampler(rt).sample_ode(sampling_method=m, num_steps=9)(x0, model, scale=1.5) for m in methods}
-        theirs = ref_transport.integrators.ode.sample
-        bind_reference_transport(ref_transport.integrators)
-        import torchdiffeq                 # (sys.modules holds the stand-in of _reference_transport here, never the real package)
-        stand_in = torchdiffeq.odeint
-        try:
-            torchdiffeq.odeint = None     # a call would now fail
-            for m in methods:
-                sampler = ref_transport.Sampler(rt)
-                got = sampler.sample_ode(sampling_method=m, num_steps=9)(x0, model, scale=1.5)
-                assert got.shape == want[m].shape and torch.allclose(got, want[m], rtol=1e-4, atol=2e-5, equal_nan=True), (m, float((got - want[m]).abs().max()))
-        finally:
-            torchdiffeq.odeint = stand_in
-            ref_transport.integrators.ode.sample = theirs
+        ref_transport.integrators.odeint = None     # a call would now fail
+        for m in methods:
+            sampler = ref_transport.Sampler(rt)
+            got = sampler.sample_ode(sampling_method=m, num_steps=9)(x0, model, scale=1.5)
+            assert got.shape == want[m].shape and torch.allclose(got, want[m], rtol=1e-4, atol=2e-5, equal_nan=True), (m, float((got - want[m]).abs().max()))
     finally:
-        restore()
+        ref_transport.integrators.odeint = stand_in
+        ref_transport.integrators.ode.sample = theirs
 
 
 def test_minimal_sampler_refuses_what_it_does_not_carry():
@@ -365,8 +422,9 @@ def test_minimal_sampler_refuses_what_it_does_not_carry():
 
 
 def test_transport_surface_and_reference_plumbing():
-    """Sampler(create_transport(GVP, velocity)).sample_ode(...) against the REFERENCE'S transport/*.py imported with the
-    oracle integrator standing in for torchdiffeq (and a stub for sgm.util): interval, grid and drift must agree."""
+    """Sampler(create_transport(GVP, velocity)).sample_ode(...) against the REFERENCE'S transport/*.py (its result recorded in
+    tests/golden/transport_ref.pt by tests/golden/make_transport_golden.py, with the oracle integrator standing in for torchdiffeq):
+    interval, grid and drift must agree."""
     from gaussiananything_amd.transport import Sampler, create_transport
     f = lambda x, t, scale=1.0: -scale * x * (1 + t.view(-1, 1))  # noqa: E731
     x0 = torch.tensor([[1.0, 2.0], [0.5, -1.0]])
@@ -374,41 +432,10 @@ def test_transport_surface_and_reference_plumbing():
     assert tr.check_interval(tr.train_eps, tr.sample_eps, sde=False, eval=True) == (0, 1)
     ours = Sampler(tr).sample_ode(sampling_method="euler", num_steps=25)(x0, f, scale=2.0)
     assert ours.shape == (25, 2, 2)
-    ref_root = "/root/reference"
-    if not os.path.isdir(ref_root):
-        pytest.skip("reference tree not present (GPU box)")
-    import types
-    from oracle import ode as oo
-
-    def fake_odeint(fn, x, t, method, atol, rtol):
-        return torch.from_numpy(oo.odeint(lambda ts, y: fn(torch.tensor(ts, dtype=torch.float32),
-                                                            torch.from_numpy(y).float()).numpy(),
-                                          x.numpy(), t.numpy(), method=method, atol=atol[0], rtol=rtol[0])).float()
-
-    saved = {k: sys.modules.get(k) for k in ("torchdiffeq", "sgm", "sgm.util", "transport")}
-    sys.modules["torchdiffeq"] = types.SimpleNamespace(odeint=fake_odeint)
-    sys.modules["sgm"] = types.ModuleType("sgm")
-    sys.modules["sgm.util"] = types.SimpleNamespace(instantiate_from_config=lambda *a, **k: None)
-    sys.path.insert(0, ref_root)
-    try:
-        for k in [k for k in sys.modules if k == "transport" or k.startswith("transport.")]:
-            del sys.modules[k]
-        import transport as ref_transport
-        rt = ref_transport.create_transport("GVP", "velocity", None, None, None, snr_type="uniform")
-        try:
-            sampler = ref_transport.Sampler(rt, guider_config=None)
-        except TypeError:
-            sampler = ref_transport.Sampler(rt)
-        ref = sampler.sample_ode(sampling_method="euler", num_steps=25)(x0, f, scale=2.0)
-    finally:
-        sys.path.remove(ref_root)
-        for k in [k for k in sys.modules if k == "transport" or k.startswith("transport.")]:
-            del sys.modules[k]
-        for k, v in saved.items():
-            if v is not None:
-                sys.modules[k] = v
-            else:
-                sys.modules.pop(k, None)
+    golden = torch.load(synthetic.fixture_path("transport_ref.pt"))["plumbing"]
+    assert torch.equal(golden["x0"], x0) and golden["scale"] == 2.0 and golden["num_steps"] == 25
+    ref = golden["euler"]
+    assert ref.shape == ours.shape
     assert float((ours - ref).abs().max()) < 1e-5
 
 

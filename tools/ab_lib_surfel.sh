@@ -13,7 +13,7 @@ for r in 1 2; do
   for name in main "$@"; do
     if [ "$name" = main ]; then cp /tmp/main_backup.so $MAIN; else cp $R/tools/_build/$name/libga_mi355.so $MAIN; fi
     for scene in surface stress; do
-      echo -n "$name $scene: "; python bench.py --scene $scene --no-dit --no-cpu-baseline --no-parity --no-extras 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['stage_ms'])"
+      echo -n "$name $scene: "; python bench.py --full --scene $scene --no-dit --no-cpu-baseline --no-parity --no-extras 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['stage_ms'])"
     done
   done
 done

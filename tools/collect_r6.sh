@@ -8,7 +8,7 @@ tag=${1:-r6}
 out=$R/gpurun_out/$tag
 mkdir -p $out
 cd $R
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err
 bash tools/trace_surfel.sh $tag/surfel_trace > $out/surfel_kernel_stats.txt 2>&1
 bash tools/trace_sampler.sh $tag/sampler_euler DiT-PixArt-PCD-CLAY-L 30 euler > $out/dit_L_euler_kernel_stats.txt 2>&1
 bash tools/trace_sampler.sh $tag/sampler_dopri5 DiT-PixArt-PCD-CLAY-L 250 dopri5 > $out/dit_L_dopri5_kernel_stats.txt 2>&1
@@ -45,12 +45,12 @@ done
 # the multi-rank code path at world size 1: RCCL process group, the gather of the rendered views inside the timed cascade sample
 cd $R
 {
-echo "# GA_BENCH_FORCE_DIST=1 RANK=0 WORLD_SIZE=1 python bench.py --no-cpu-baseline --no-parity --no-extras under rocprofv3 --kernel-trace --stats:"
+echo "# GA_BENCH_FORCE_DIST=1 RANK=0 WORLD_SIZE=1 python bench.py --full --no-cpu-baseline --no-parity --no-extras under rocprofv3 --kernel-trace --stats:"
 echo "# init_process_group('nccl') = RCCL, dist.gather of the [8,10,512,512] payload after the timed steps and of [8,9,512,512] inside cascade_per_rank"
 cd /tmp
 rm -rf /tmp/tr_dist
 GA_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 HSA_ENABLE_IPC_MODE_LEGACY=0 timeout 600 \
-  rocprofv3 --kernel-trace --stats -d /tmp/tr_dist -o x -- python $R/bench.py --no-cpu-baseline --no-parity --no-extras > $out/dist_bench.json 2> $out/dist_bench.err
+  rocprofv3 --kernel-trace --stats -d /tmp/tr_dist -o x -- python $R/bench.py --full --no-cpu-baseline --no-parity --no-extras > $out/dist_bench.json 2> $out/dist_bench.err
 python $R/tools/rocpd_stats.py $(ls /tmp/tr_dist/*.db /tmp/tr_dist/*/*.db 2>/dev/null | head -1) | grep -i "rccl\|nccl\|ncclDevKernel\|copyBuffer\|Generic" | head -12
 python -c "import json,sys; d=json.loads(open('$out/dist_bench.json').read().strip().splitlines()[-1]); print({k: d.get(k) for k in ('n_gpus','rccl_ranks','value','sec_per_sample')}, d['config'].get('gather_ms'), d.get('cascade',{}).get('gathered_shape'))"
 } > $out/dist_world1.txt 2>&1

@@ -7,6 +7,6 @@ for r in 1 2; do
   for kv in "$@"; do
     vg=${kv%%:*}; sp=${kv##*:}
     echo -n "GA_PRE_VIEWS=$vg GA_PRE_SPLATS=$sp: "
-    GA_PRE_NT=${NT:-0} GA_PRE_VIEWS=$vg GA_PRE_SPLATS=$sp python bench.py --no-dit --no-cpu-baseline --no-parity --no-extras 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['stage_ms'])"
+    GA_PRE_NT=${NT:-0} GA_PRE_VIEWS=$vg GA_PRE_SPLATS=$sp python bench.py --full --no-dit --no-cpu-baseline --no-parity --no-extras 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['ms_per_step'], d['stage_ms'])"
   done
 done
