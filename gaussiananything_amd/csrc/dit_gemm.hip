@@ -951,15 +951,72 @@ extern "C" size_t ga_gemm_splitk_workspace_bytes(int32_t M, int32_t N)
     return GA_GEMM_SPLITK_COUNTER_BYTES + tiles * 4 * 192 * 128 * 4;   // (two 96-row tiles x 4 splits fit the same bytes)
 }
 
-extern "C" int ga_gemm_bf16(const GaGemmArgs *a, void *stream)
+namespace gadit {
+// Every kernel instance the dispatcher can launch, one entry per (instance, epilogue): ga_gemm_bf16 looks its plan up in this table,
+// and ga_gemm_instances exports it (tests/test_gemm_plan.py checks that the case table reaches every entry the rules can pick).
+struct GemmInstance {
+    GaGemmPlan shape;   // family ... lds_bytes; grid, xmap and wt are per call
+    const void *fn;
+};
+#define GA_INST(FAM, E, TM, TN, WV, NSTV, RV, MTV, SPL, LDS, ...) \
+    {{GA_GEMM_FAMILY_##FAM, E, TM, TN, WV, NSTV, RV, MTV, SPL, 0, 0, 0, 0, 0, LDS}, (const void *)__VA_ARGS__},
+// the four ring tiles: 192 x 128 / 8 waves and 96 x 128 / 4 waves (k-step pipeline), 96 x 64 and 64 x 64 / 4 waves
+#define GA_RING_TILES(E, NSTV, RV)                                                                                              \
+    GA_INST(RING, E, 192, 128, 8, NSTV, RV, 0, 1, NSTV * 320 * BK * 2, &gemm_ring_kernel<E, 4, 2, 3, 4, NSTV, 2, 0, RV>)         \
+    GA_INST(RING, E, 96, 128, 4, NSTV, RV, 0, 1, NSTV * 224 * BK * 2, &gemm_ring_kernel<E, 2, 2, 3, 4, NSTV, 2, 0, RV>)          \
+    GA_INST(RING, E, 96, 64, 4, NSTV, RV, 0, 1, NSTV * 160 * BK * 2, &gemm_ring_kernel<E, 2, 2, 3, 2, NSTV, 0, 0, RV>)           \
+    GA_INST(RING, E, 64, 64, 4, NSTV, RV, 0, 1, NSTV * 128 * BK * 2, &gemm_ring_kernel<E, 4, 1, 1, 4, NSTV, 0, 0, RV>)
+// four slots; four slots with two remainder tiles; three slots (the last two: K / 64 no multiple of 4, no fp32 store)
+#define GA_RING_EPI(E) GA_RING_TILES(E, 4, 0) GA_RING_TILES(E, 4, 2) GA_RING_TILES(E, 3, 0)
+#define GA_GENERAL_MT(E, NSTV, MTV) GA_INST(GENERAL, E, 32 * MTV, 128, 4, NSTV, 0, MTV, 1, NSTV * (BN + 32 * MTV) * BK * 2, &gemm_bf16_kernel<E, NSTV, MTV>)
+#define GA_GENERAL_EPI(E)                                                                                                       \
+    GA_GENERAL_MT(E, 4, 4) GA_GENERAL_MT(E, 4, 3) GA_GENERAL_MT(E, 4, 2) GA_GENERAL_MT(E, 4, 1)                                 \
+    GA_GENERAL_MT(E, 2, 4) GA_GENERAL_MT(E, 2, 3) GA_GENERAL_MT(E, 2, 2) GA_GENERAL_MT(E, 2, 1)
+static const GemmInstance g_gemm_instances[] = {
+    GA_RING_EPI(0) GA_RING_EPI(1) GA_RING_EPI(2) GA_RING_TILES(3, 4, 0)
+    GA_GENERAL_EPI(0) GA_GENERAL_EPI(1) GA_GENERAL_EPI(2) GA_GENERAL_EPI(3)
+    // split-K configurations (ga_gemm_splitk_mode): 1: 192 x 128 x 4 splits, 2: 96 x 128 x 2, 3: 96 x 128 x 4, 4: 192 x 128 x 2
+    GA_INST(SPLITK, 2, 192, 128, 8, 4, 0, 0, 4, 4 * 320 * BK * 2, &gemm_ring_kernel<2, 4, 2, 3, 4, 4, 2, 4>)
+    GA_INST(SPLITK, 2, 96, 128, 4, 4, 0, 0, 2, 4 * 224 * BK * 2, &gemm_ring_kernel<2, 2, 2, 3, 4, 4, 2, 2>)
+    GA_INST(SPLITK, 2, 96, 128, 4, 4, 0, 0, 4, 4 * 224 * BK * 2, &gemm_ring_kernel<2, 2, 2, 3, 4, 4, 2, 4>)
+    GA_INST(SPLITK, 0, 192, 128, 8, 4, 0, 0, 2, 4 * 320 * BK * 2, &gemm_ring_kernel<0, 4, 2, 3, 4, 4, 2, 2>)
+    GA_INST(SPLITK, 1, 192, 128, 8, 4, 0, 0, 2, 4 * 320 * BK * 2, &gemm_ring_kernel<1, 4, 2, 3, 4, 4, 2, 2>)
+    GA_INST(SPLITK, 2, 192, 128, 8, 4, 0, 0, 2, 4 * 320 * BK * 2, &gemm_ring_kernel<2, 4, 2, 3, 4, 4, 2, 2>)
+};
+#undef GA_GENERAL_EPI
+#undef GA_GENERAL_MT
+#undef GA_RING_EPI
+#undef GA_RING_TILES
+#undef GA_INST
+constexpr int kGemmInstances = (int)(sizeof(g_gemm_instances) / sizeof(g_gemm_instances[0]));
+
+static bool same_instance(const GaGemmPlan &a, const GaGemmPlan &b)
 {
-    using namespace gadit;
+    return a.family == b.family && a.epilogue == b.epilogue && a.tile_m == b.tile_m && a.tile_n == b.tile_n && a.waves == b.waves &&
+           a.slots == b.slots && a.rem == b.rem && a.mt == b.mt && a.splits == b.splits;
+}
+
+static int env_int(const char *name, int dflt)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+static void set_plan(GaGemmPlan *pl, int family, int tile_m, int tile_n, int waves, int slots, int rem, int mt, int splits, int gx, int gy, int gz)
+{
+    pl->family = family; pl->tile_m = tile_m; pl->tile_n = tile_n; pl->waves = waves; pl->slots = slots; pl->rem = rem; pl->mt = mt;
+    pl->splits = splits; pl->grid_x = gx; pl->grid_y = gy; pl->grid_z = gz;
+}
+
+// The argument checks and the whole launch choice of ga_gemm_bf16 -- family, tile, ring, split-K, grid, xmap, write-through -- from the
+// arguments alone (no HIP call).  The instance's LDS size comes from g_gemm_instances.
+static int gemm_plan(const GaGemmArgs *a, GaGemmPlan *pl)
+{
     if (!a || !a->A || !a->W || !a->out) return GA_DIT_ERR_NULL_ARG;
     if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->K % BK != 0 || a->N % 4 != 0 || a->lda % 8 != 0 || a->ldo % 4 != 0 ||
         a->lda < a->K)
         return GA_DIT_ERR_BAD_SHAPE;
     if (a->epilogue == GA_GEMM_EPI_RESIDUAL && a->gate && a->rows_per_batch <= 0) return GA_DIT_ERR_BAD_SHAPE;
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (a->vt && (a->epilogue != GA_GEMM_EPI_STORE_BF16 || a->vt_col0 % 64 != 0 || (a->N - a->vt_col0) % 64 != 0 ||
                   a->rows_per_batch <= 0 || a->vt_ld < a->rows_per_batch))
         return GA_DIT_ERR_BAD_SHAPE;
@@ -974,22 +1031,21 @@ extern "C" int ga_gemm_bf16(const GaGemmArgs *a, void *stream)
     if (a->row_ss && ((a->epilogue != GA_GEMM_EPI_STORE_BF16 && a->epilogue != GA_GEMM_EPI_GELU_BF16) || a->row_ss_tiles <= 0 ||
                       a->row_ss_tiles > 20 || a->row_ss_dim <= 0 || (uintptr_t)a->row_ss % 16 != 0))
         return GA_DIT_ERR_BAD_SHAPE;
-    // (more than 16 partial sums per row: only the three-slot ring instances and the 2-slot general kernel read a fifth group)
-    const bool wide_ss = a->row_ss && a->row_ss_tiles > 16;
     if ((a->emit_w || a->emit_scale) && (!a->emit_x || !a->emit_w || !a->emit_scale || a->rows_per_batch <= 0 || a->emit_scale_stride % 4 != 0))
         return GA_DIT_ERR_BAD_SHAPE;
     if (a->bias_stride && (!a->bias || a->rows_per_batch <= 0 || a->bias_stride % 4 != 0 || a->bias_stride < a->N)) return GA_DIT_ERR_BAD_SHAPE;
     if (a->k_rows && (a->epilogue != GA_GEMM_EPI_RESIDUAL || a->k_rows < 0 || a->k_rows > a->M)) return GA_DIT_ERR_BAD_SHAPE;
-    GemmP p{a->M, a->N, a->K, a->rows_per_batch, a->A, a->W, a->bias, a->gate, a->out, a->lda, a->ldo, a->gate_stride,
-                  a->vt, a->vt_col0, a->vt ? (a->N - a->vt_col0) / 64 : 0, a->vt_ld, a->qk_w0, a->qk_w1, a->qk_cols0,
-                  a->qk_cols1, a->emit_x, a->emit_ss, a->emit_ld, a->row_ss, a->row_ss_tiles,
-                  a->row_ss_dim > 0 ? 1.0f / (float)a->row_ss_dim : 0.f, a->row_ss_eps, a->w_tiled ? 1 : 0,
-                  a->emit_w, a->emit_scale, a->emit_scale_stride, a->bias_stride, a->k_rows == a->M ? 0 : a->k_rows,
-                  0, nullptr, nullptr, 0, 0};
+    // (checked before the choice: the split-K branch below used to launch the GELU instance for an unknown epilogue)
+    if (a->epilogue < GA_GEMM_EPI_STORE_BF16 || a->epilogue > GA_GEMM_EPI_STORE_F32) return GA_DIT_ERR_BAD_SHAPE;
+    // (more than 16 partial sums per row: only the three-slot ring instances and the 2-slot general kernel read a fifth group)
+    const bool wide_ss = a->row_ss && a->row_ss_tiles > 16;
+    const int k_rows = a->k_rows == a->M ? 0 : a->k_rows;
+    *pl = GaGemmPlan{};
+    pl->epilogue = a->epilogue;
     {   // write-through output stores (st16): same-box A/B (profiles/r6_wt_ab.txt) DiT-L at CFG batch 2 2.730 -> 2.691 ms per evaluation, DiT-B
         // 1.244 -> 1.234, batch 1 -0.3 %, CFG batch 4 +0.4 %: on for the one-round grids.  GA_GEMM_WT: 0 off, 1 always, 2 (default) M <= 2048
-        static const int wt_env = [] { const char *e = getenv("GA_GEMM_WT"); return e ? atoi(e) : 2; }();
-        p.wt = wt_env == 1 || (wt_env == 2 && a->M <= 2048);
+        static const int wt_env = env_int("GA_GEMM_WT", 2);
+        pl->wt = wt_env == 1 || (wt_env == 2 && a->M <= 2048);
     }
     // Tile / ring choice (256 CUs).  A workgroup tile is 128 weight rows x 32 MT activation rows (MT = 4, 3, 2, 1); its work is
     // proportional to MT plus a tile-independent share (prologue, weight tile, epilogue: about one MT unit, tools/gemm_sweep.py) and
@@ -1008,7 +1064,9 @@ extern "C" int ga_gemm_bf16(const GaGemmArgs *a, void *stream)
     // Round 6: deterministic split-K for the GEMMs whose output tiles cannot fill the chip (FusedMLP's second linear: K = 4 D; the wide
     // projections at 768 rows).  At M <= 1536 rows the chip is only filled by 96 x 64 / 64 x 64 tiles, which pull 1.3 MB of operands through
     // every CU's L1 miss path (the bound of these kernels); 192 x 128 tiles over a quarter of K each halve that.
-    if (a->splitk_ws && p.k_rows == 0 && a->epilogue != GA_GEMM_EPI_STORE_F32) {
+    // (not with more than 16 row partial sums: the split instances prefetch 16 of them -- a K they can split is a multiple of 512, where
+    //  the header allows no more than 16, but the unsplit choice below serves such calls correctly)
+    if (a->splitk_ws && k_rows == 0 && a->epilogue != GA_GEMM_EPI_STORE_F32 && !wide_ss) {
         const int sk_env = splitk_mode().load(std::memory_order_relaxed);
         const int nk = a->K / BK;
         const bool per_batch = a->bias_stride != 0 || a->emit_scale != nullptr;
@@ -1040,26 +1098,9 @@ extern "C" int ga_gemm_bf16(const GaGemmArgs *a, void *stream)
         const size_t tile_bytes = (size_t)(big ? 192 : 96) * 128 * 4;
         if (cfg && tiles <= GA_GEMM_SPLITK_MAX_TILES &&
             (size_t)a->splitk_ws_bytes >= GA_GEMM_SPLITK_COUNTER_BYTES + (size_t)tiles * splits * tile_bytes && ((uintptr_t)a->splitk_ws & 255) == 0) {
-            GemmP q = p;
-            q.splits = splits;
-            q.sk_count = static_cast<unsigned *>(a->splitk_ws);
-            q.sk_part = reinterpret_cast<float *>(static_cast<char *>(a->splitk_ws) + GA_GEMM_SPLITK_COUNTER_BYTES);
-            const dim3 gbig((unsigned)((a->N + 127) / 128), (unsigned)((a->M + 191) / 192), (unsigned)splits);
-            const dim3 gmid((unsigned)((a->N + 127) / 128), (unsigned)((a->M + 95) / 96), (unsigned)splits);
-            // (the LDS opt-in belongs to the function on one device; setting it is cheap and idempotent)
-#define GA_SK_LAUNCH(KERNEL, GRID, THREADS, LDS)                                                                                   \
-            do {                                                                                                                  \
-                if (hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return GA_DIT_ERR_LAUNCH; \
-                hipLaunchKernelGGL(KERNEL, GRID, dim3(THREADS), LDS, s, q);                                                       \
-            } while (0)
-            if (cfg == 1) GA_SK_LAUNCH((gemm_ring_kernel<2, 4, 2, 3, 4, 4, 2, 4>), gbig, 512, 4 * 320 * BK * 2);
-            else if (cfg == 2) GA_SK_LAUNCH((gemm_ring_kernel<2, 2, 2, 3, 4, 4, 2, 2>), gmid, 256, 4 * 224 * BK * 2);
-            else if (cfg == 3) GA_SK_LAUNCH((gemm_ring_kernel<2, 2, 2, 3, 4, 4, 2, 4>), gmid, 256, 4 * 224 * BK * 2);
-            else if (a->epilogue == GA_GEMM_EPI_RESIDUAL) GA_SK_LAUNCH((gemm_ring_kernel<2, 4, 2, 3, 4, 4, 2, 2>), gbig, 512, 4 * 320 * BK * 2);
-            else if (a->epilogue == GA_GEMM_EPI_STORE_BF16) GA_SK_LAUNCH((gemm_ring_kernel<0, 4, 2, 3, 4, 4, 2, 2>), gbig, 512, 4 * 320 * BK * 2);
-            else GA_SK_LAUNCH((gemm_ring_kernel<1, 4, 2, 3, 4, 4, 2, 2>), gbig, 512, 4 * 320 * BK * 2);
-#undef GA_SK_LAUNCH
-            return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH;
+            set_plan(pl, GA_GEMM_FAMILY_SPLITK, big ? 192 : 96, 128, big ? 8 : 4, 4, 0, 0, splits, (a->N + 127) / 128,
+                     (a->M + (big ? 191 : 95)) / (big ? 192 : 96), splits);
+            return GA_DIT_OK;
         }
     }
     {
@@ -1077,15 +1118,15 @@ extern "C" int ga_gemm_bf16(const GaGemmArgs *a, void *stream)
         // round 6: 96 x 128, four waves of 48 x 64 (the wave tile of the 192 x 128 kernel): for the wide projections at 768 rows, whose 96 x 64
         // grid is 1.5 - 2 workgroups per CU (qkv 384, fc1 512) while this one is 192 / 256 with 30 % fewer operand bytes on the busiest CU
         // same-box A/B (profiles/r6_ring4_ab.txt): DiT-L on the conditional sequence alone 2.376 -> 2.315 ms per evaluation, nothing else moves.  GA_GEMM_RING4=0: off
-        static const int ring4_env = [] { const char *e = getenv("GA_GEMM_RING4"); return e ? atoi(e) : 1; }();
+        static const int ring4_env = env_int("GA_GEMM_RING4", 1);
         // (a 48 x 64 two-wave tile that would give the N = 1024 residual GEMMs at 768 rows 256 workgroups instead of 192 measured 3 % slower per evaluation: not kept)
         const long long wg_96x128 = (long long)((a->N + 127) / 128) * ((a->M + 95) / 96);
-        static const int ragged3_env = [] { const char *e = getenv("GA_GEMM_RAGGED3"); return e ? atoi(e) : 1; }();
+        static const int ragged3_env = env_int("GA_GEMM_RAGGED3", 1);
         // round 6: K that is no multiple of 256 but one of 192 (DiT-PixArt-PCD-CLAY-XL: 1152, 4608) runs the same tiles on a ring of THREE slots
         // ... and, better (the same shapes ran 1.5 x longer on three slots: two tiles in flight per DMA latency instead of three): the FOUR-slot
         // ring with two remainder tiles in its peeled tail where K is 2 tiles past a multiple of 4 (1152 = 18 tiles); three slots for what is left
         // (GA_GEMM_REM=0: three slots as before, A/B aid)
-        static const int rem_env = [] { const char *e = getenv("GA_GEMM_REM"); return e ? atoi(e) : 1; }();
+        static const int rem_env = env_int("GA_GEMM_REM", 1);
         int nst_ring = 0, rem = 0;
         if (nk % 4 == 0 && nk >= 8) nst_ring = wide_ss ? 0 : 4;
         else if (rem_env && nk % 4 == 2 && nk >= 10) { nst_ring = 4; rem = 2; }
@@ -1094,11 +1135,11 @@ extern "C" int ga_gemm_bf16(const GaGemmArgs *a, void *stream)
         if (nst_ring) {
             // (round 6: 144 instead of 160 -- DiT-B's qkv, 18 x 8 workgroups, is better off on this tile than on 864 of 64 x 64: 1.237 -> 1.222 ms per
             //  evaluation same-box; nothing else falls between the two.  GA_GEMM_BIGMIN: A/B aid)
-            static const int bigmin = [] { const char *e = getenv("GA_GEMM_BIGMIN"); return e ? atoi(e) : 144; }();
+            static const int bigmin = env_int("GA_GEMM_BIGMIN", 144);
             // (a 192 x 128 grid of a little over one round -- XL's fc1, 36 x 8 = 288 workgroups on 256 CUs -- pays two rounds for 1.1: 37.8 us
             //  against 28.2 on the 2-slot 128 x 128 kernel below, 432 workgroups two to a CU; the rule is confined to the three-slot shapes so
             //  that no released model's choice moves)
-            static const int ragged_env = [] { const char *e = getenv("GA_GEMM_RAGGED"); return e ? atoi(e) : 1; }();
+            static const int ragged_env = env_int("GA_GEMM_RAGGED", 1);
             const bool ragged_big = ragged_env && odd_k && wg_big > 256 && wg_big * 4 < ((wg_big + 255) / 256) * 256 * 3;
             if (odd_k && (a->epilogue == GA_GEMM_EPI_STORE_F32 || ragged_big)) ring = 0;   // (no such instance of the fp32 store: nothing asks for it)
             else if (wg_big >= bigmin && rows48) ring = 1;
@@ -1124,67 +1165,25 @@ extern "C" int ga_gemm_bf16(const GaGemmArgs *a, void *stream)
         // (round 6: a 96-row x 192-column six-wave tile that fills all 256 CUs for DiT-L's qkv -- 16 x 16 workgroups instead of the 24 x 8
         //  = 192 of the 192 x 128 tile, 36 KB per K-tile instead of 40 -- measured the same to the microsecond, same-box A/B
         //  2.72 / 2.72 ms per evaluation: not kept)
+        // (round 6: a deeper ring -- 6 or 8 slots of the 96 x 64 tile, 120 / 160 KiB -- for the residual GEMMs that run one workgroup per CU
+        //  measured no gain, DiT-L 2.79 -> 2.81 / 2.83 ms per evaluation same-box: unlike the 192 x 128 tile at K = 1152, whose step from three
+        //  slots to four was worth 1.27 x, these are not bound by the tiles in flight)
         if (ring) {
-            // (the LDS opt-in belongs to the function ON ONE DEVICE: one flag per device, set by whichever thread gets there -- idempotent)
-            static std::atomic<bool> ring_attr_dev[64];
-            int dev_ = 0;
-            (void)hipGetDevice(&dev_);
-            std::atomic<bool> &ring_attr_set = ring_attr_dev[dev_ >= 0 && dev_ < 64 ? dev_ : 63];
-            if (!ring_attr_set.load(std::memory_order_acquire) || dev_ >= 64) {
-#define GA_RATTR(E)                                                                                                       \
-                (void)hipFuncSetAttribute((const void *)gemm_ring_kernel<E, 4, 2, 3, 4, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 320 * BK * 2); \
-                (void)hipFuncSetAttribute((const void *)gemm_ring_kernel<E, 2, 2, 3, 2, 4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 160 * BK * 2); \
-                (void)hipFuncSetAttribute((const void *)gemm_ring_kernel<E, 4, 1, 1, 4, 4, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 128 * BK * 2);
-                GA_RATTR(0) GA_RATTR(1) GA_RATTR(2) GA_RATTR(3)
-#undef GA_RATTR
-                ring_attr_set.store(true, std::memory_order_release);
-            }
+            const int tm = ring == 1 ? 192 : (ring == 3 ? 64 : 96), tn = (ring == 1 || ring == 4) ? 128 : 64;
+            set_plan(pl, GA_GEMM_FAMILY_RING, tm, tn, ring == 1 ? 8 : 4, nst_ring, rem, 0, 1, (a->N + tn - 1) / tn, (a->M + tm - 1) / tm, 1);
             // tile -> XCD blocking for the residual GEMMs on the 96 x 64 / 64 x 64 tiles (GemmP.xmap).  Same-box A/B (profiles/r6_xmap_ab.txt):
             // it pays where the natural dealing is ragged or the grid is more than one round -- DiT-B (12 tile columns: an XCD's
             // workgroups share neither weights nor activations systematically) 1.267 -> 1.229 ms per evaluation, DiT-L at CFG batch 4
             // (512 workgroups) 5.21 -> 5.10 -- and costs 1 % where every XCD already owns two whole tile columns of a one-round grid
             // (DiT-L at CFG batch 2: 2.930 -> 2.960; batch 1: 2.409 -> 2.422).  GA_GEMM_XMAP: 0 off, 1 always (where the grid divides), 2 (default) by that rule
-            static const int xmap_env = [] { const char *e = getenv("GA_GEMM_XMAP"); return e ? atoi(e) : 2; }();
-            GemmP pr = p;
-            {
-                const unsigned gx = ring == 2 ? (unsigned)((a->N + 63) / 64) : (ring == 3 ? (unsigned)((a->N + 63) / 64) : 1u);
-                const unsigned gy = ring == 2 ? (unsigned)((a->M + 95) / 96) : (ring == 3 ? (unsigned)((a->M + 63) / 64) : 1u);
+            static const int xmap_env = env_int("GA_GEMM_XMAP", 2);
+            if (ring == 2 || ring == 3) {
+                const unsigned gx = (unsigned)pl->grid_x, gy = (unsigned)pl->grid_y;
                 const bool pays = xmap_env == 1 || (xmap_env == 2 && (gx % 8 != 0 || gx * gy > 256));
-                if (pays && ring != 1 && a->epilogue == GA_GEMM_EPI_RESIDUAL && gx % 2 == 0 && gy % 4 == 0 && (gx * gy) % 8 == 0) pr.xmap = 1;
+                if (pays && a->epilogue == GA_GEMM_EPI_RESIDUAL && gx % 2 == 0 && gy % 4 == 0 && (gx * gy) % 8 == 0) pl->xmap = 1;
             }
             // (round 6: the k-step software pipeline of the 192 x 128 kernel on the 96 x 64 tile measured 1.5 - 2 % slower per evaluation: not kept)
-#define GA_RLAUNCH_N(E, NSTV, RV)                                                                                         \
-            if (ring == 4) {                                                                                              \
-                if (hipFuncSetAttribute((const void *)gemm_ring_kernel<E, 2, 2, 3, 4, NSTV, 2, 0, RV>, hipFuncAttributeMaxDynamicSharedMemorySize, NSTV * 224 * BK * 2) != hipSuccess) return GA_DIT_ERR_LAUNCH; \
-                hipLaunchKernelGGL((gemm_ring_kernel<E, 2, 2, 3, 4, NSTV, 2, 0, RV>), dim3((unsigned)((a->N + 127) / 128), (unsigned)((a->M + 95) / 96)), \
-                                   dim3(256), NSTV * 224 * BK * 2, s, p);                                                 \
-            } else if (ring == 1) {                                                                                       \
-                if ((NSTV != 4 || RV != 0) && hipFuncSetAttribute((const void *)gemm_ring_kernel<E, 4, 2, 3, 4, NSTV, 2, 0, RV>, hipFuncAttributeMaxDynamicSharedMemorySize, NSTV * 320 * BK * 2) != hipSuccess) return GA_DIT_ERR_LAUNCH; \
-                hipLaunchKernelGGL((gemm_ring_kernel<E, 4, 2, 3, 4, NSTV, 2, 0, RV>), dim3((unsigned)((a->N + 127) / 128), (unsigned)((a->M + 191) / 192)), \
-                                   dim3(512), NSTV * 320 * BK * 2, s, p);                                                 \
-            } else if (ring == 2) {                                                                                       \
-                if ((NSTV != 4 || RV != 0) && hipFuncSetAttribute((const void *)gemm_ring_kernel<E, 2, 2, 3, 2, NSTV, 0, 0, RV>, hipFuncAttributeMaxDynamicSharedMemorySize, NSTV * 160 * BK * 2) != hipSuccess) return GA_DIT_ERR_LAUNCH; \
-                hipLaunchKernelGGL((gemm_ring_kernel<E, 2, 2, 3, 2, NSTV, 0, 0, RV>), dim3((unsigned)((a->N + 63) / 64), (unsigned)((a->M + 95) / 96)), \
-                                   dim3(256), NSTV * 160 * BK * 2, s, pr);                                                \
-            } else {                                                                                                      \
-                if ((NSTV != 4 || RV != 0) && hipFuncSetAttribute((const void *)gemm_ring_kernel<E, 4, 1, 1, 4, NSTV, 0, 0, RV>, hipFuncAttributeMaxDynamicSharedMemorySize, NSTV * 128 * BK * 2) != hipSuccess) return GA_DIT_ERR_LAUNCH; \
-                hipLaunchKernelGGL((gemm_ring_kernel<E, 4, 1, 1, 4, NSTV, 0, 0, RV>), dim3((unsigned)((a->N + 63) / 64), (unsigned)((a->M + 63) / 64)), \
-                                   dim3(256), NSTV * 128 * BK * 2, s, pr);                                                \
-            }
-            // (round 6: a deeper ring -- 6 or 8 slots of the 96 x 64 tile, 120 / 160 KiB -- for the residual GEMMs that run one workgroup per CU
-            //  measured no gain, DiT-L 2.79 -> 2.81 / 2.83 ms per evaluation same-box: unlike the 192 x 128 tile at K = 1152, whose step from three
-            //  slots to four was worth 1.27 x, these are not bound by the tiles in flight)
-#define GA_RLAUNCH(E) if (nst_ring == 4 && rem == 0) { GA_RLAUNCH_N(E, 4, 0) } else if (nst_ring == 4) { GA_RLAUNCH_N(E, 4, 2) } else { GA_RLAUNCH_N(E, 3, 0) }
-            switch (a->epilogue) {
-            case GA_GEMM_EPI_STORE_BF16: GA_RLAUNCH(0) break;
-            case GA_GEMM_EPI_GELU_BF16: GA_RLAUNCH(1) break;
-            case GA_GEMM_EPI_RESIDUAL: GA_RLAUNCH(2) break;
-            case GA_GEMM_EPI_STORE_F32: GA_RLAUNCH_N(3, 4, 0) break;     // (odd_k never gets here)
-            default: return GA_DIT_ERR_BAD_SHAPE;
-            }
-#undef GA_RLAUNCH_N
-#undef GA_RLAUNCH
-            return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH;
+            return GA_DIT_OK;
         }
     }
     const long long ncols = (a->N + BN - 1) / BN;
@@ -1195,46 +1194,77 @@ extern "C" int ga_gemm_bf16(const GaGemmArgs *a, void *stream)
         const long long cost = ((wgs + 255) / 256) * (cand + 1);
         if (best < 0 || cost < best) { best = cost; mt = cand; }
     }
-    long long wgs = ncols * ((a->M + 32 * mt - 1) / (32 * mt));
+    const long long wgs = ncols * ((a->M + 32 * mt - 1) / (32 * mt));
     int nst = (wgs > 256 || wide_ss) ? 2 : 4;
 #ifdef GA_TUNING  // tuning builds only: GA_GEMM_CFG = 10 * MT + ring slots
     if (const char *e = getenv("GA_GEMM_CFG")) { const int c = atoi(e); if (c / 10 >= 1 && c / 10 <= 4 && (c % 10 == 2 || c % 10 == 4)) { mt = c / 10; nst = c % 10; } }
 #endif
-    static std::atomic<bool> attr_dev[64];
-    int dev2_ = 0;
-    (void)hipGetDevice(&dev2_);
-    std::atomic<bool> &attr_set = attr_dev[dev2_ >= 0 && dev2_ < 64 ? dev2_ : 63];
-    if (!attr_set.load(std::memory_order_acquire) || dev2_ >= 64) {  // > 64 KiB of dynamic LDS has to be opted into once per kernel and device
-#define GA_ATTR(E)                                                                                                  \
-        (void)hipFuncSetAttribute((const void *)gemm_bf16_kernel<E, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  4 * (BN + 128) * BK * 2);                                                          \
-        (void)hipFuncSetAttribute((const void *)gemm_bf16_kernel<E, 4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  4 * (BN + 96) * BK * 2);                                                           \
-        (void)hipFuncSetAttribute((const void *)gemm_bf16_kernel<E, 4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  4 * (BN + 64) * BK * 2);                                                           \
-        (void)hipFuncSetAttribute((const void *)gemm_bf16_kernel<E, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  4 * (BN + 32) * BK * 2);
-        GA_ATTR(0) GA_ATTR(1) GA_ATTR(2) GA_ATTR(3)
-#undef GA_ATTR
-        attr_set.store(true, std::memory_order_release);
+    set_plan(pl, GA_GEMM_FAMILY_GENERAL, 32 * mt, BN, 4, nst, 0, mt, 1, (int)ncols, (a->M + 32 * mt - 1) / (32 * mt), 1);
+    return GA_DIT_OK;
+}
+
+static const GemmInstance *find_instance(const GaGemmPlan &pl)
+{
+    for (const GemmInstance &g : g_gemm_instances)
+        if (same_instance(g.shape, pl)) return &g;
+    return nullptr;
+}
+}  // namespace gadit
+
+extern "C" int ga_gemm_plan(const GaGemmArgs *a, GaGemmPlan *plan)
+{
+    using namespace gadit;
+    if (!plan) return GA_DIT_ERR_NULL_ARG;
+    GaGemmPlan pl;
+    const int rc = gemm_plan(a, &pl);
+    if (rc != GA_DIT_OK) return rc;
+    const GemmInstance *g = find_instance(pl);
+    if (!g) return GA_DIT_ERR_LAUNCH;     // (a plan without an instance: a dispatcher bug, tests/test_gemm_plan.py)
+    pl.lds_bytes = g->shape.lds_bytes;
+    *plan = pl;
+    return GA_DIT_OK;
+}
+
+extern "C" int ga_gemm_instances(GaGemmPlan *out, int32_t capacity)
+{
+    using namespace gadit;
+    for (int i = 0; out && i < kGemmInstances && i < capacity; ++i) out[i] = g_gemm_instances[i].shape;
+    return kGemmInstances;
+}
+
+extern "C" int ga_gemm_bf16(const GaGemmArgs *a, void *stream)
+{
+    using namespace gadit;
+    GaGemmPlan pl;
+    const int rc = gemm_plan(a, &pl);
+    if (rc != GA_DIT_OK) return rc;
+    const GemmInstance *gi = find_instance(pl);
+    if (!gi) return GA_DIT_ERR_LAUNCH;
+    const GemmInstance &g = *gi;
+    const int inst = (int)(gi - g_gemm_instances);
+    GemmP p{a->M, a->N, a->K, a->rows_per_batch, a->A, a->W, a->bias, a->gate, a->out, a->lda, a->ldo, a->gate_stride,
+                  a->vt, a->vt_col0, a->vt ? (a->N - a->vt_col0) / 64 : 0, a->vt_ld, a->qk_w0, a->qk_w1, a->qk_cols0,
+                  a->qk_cols1, a->emit_x, a->emit_ss, a->emit_ld, a->row_ss, a->row_ss_tiles,
+                  a->row_ss_dim > 0 ? 1.0f / (float)a->row_ss_dim : 0.f, a->row_ss_eps, a->w_tiled ? 1 : 0,
+                  a->emit_w, a->emit_scale, a->emit_scale_stride, a->bias_stride, a->k_rows == a->M ? 0 : a->k_rows,
+                  0, nullptr, nullptr, pl.xmap, pl.wt};
+    if (pl.family == GA_GEMM_FAMILY_SPLITK) {
+        p.splits = pl.splits;
+        p.sk_count = static_cast<unsigned *>(a->splitk_ws);
+        p.sk_part = reinterpret_cast<float *>(static_cast<char *>(a->splitk_ws) + GA_GEMM_SPLITK_COUNTER_BYTES);
     }
-#define GA_LAUNCH_MT(E, NSTV, MTV)                                                                                   \
-    hipLaunchKernelGGL((gemm_bf16_kernel<E, NSTV, MTV>), dim3((unsigned)ncols, (unsigned)((a->M + 32 * MTV - 1) / (32 * MTV))), \
-                       dim3(256), NSTV * (BN + 32 * MTV) * BK * 2, s, p)
-#define GA_LAUNCH(E)                                                                                                 \
-    if (nst == 2) {                                                                                                  \
-        if (mt == 4) GA_LAUNCH_MT(E, 2, 4); else if (mt == 3) GA_LAUNCH_MT(E, 2, 3);                                  \
-        else if (mt == 2) GA_LAUNCH_MT(E, 2, 2); else GA_LAUNCH_MT(E, 2, 1);                                          \
-    } else {                                                                                                         \
-        if (mt == 4) GA_LAUNCH_MT(E, 4, 4); else if (mt == 3) GA_LAUNCH_MT(E, 4, 3);                                  \
-        else if (mt == 2) GA_LAUNCH_MT(E, 4, 2); else GA_LAUNCH_MT(E, 4, 1);                                          \
+    // more than 64 KiB of dynamic LDS has to be opted into per kernel and device: once per (instance, device), by whichever thread gets
+    // there first (idempotent)
+    static std::atomic<unsigned long long> attr_set[kGemmInstances];
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = dev >= 0 && dev < 64 ? 1ull << dev : 0ull;
+    if (!bit || !(attr_set[inst].load(std::memory_order_acquire) & bit)) {
+        if (hipFuncSetAttribute(g.fn, hipFuncAttributeMaxDynamicSharedMemorySize, g.shape.lds_bytes) != hipSuccess) return GA_DIT_ERR_LAUNCH;
+        attr_set[inst].fetch_or(bit, std::memory_order_acq_rel);
     }
-    switch (a->epilogue) {
-    case GA_GEMM_EPI_STORE_BF16: GA_LAUNCH(0) break;
-    case GA_GEMM_EPI_GELU_BF16: GA_LAUNCH(1) break;
-    case GA_GEMM_EPI_RESIDUAL: GA_LAUNCH(2) break;
-    case GA_GEMM_EPI_STORE_F32: GA_LAUNCH(3) break;
-    default: return GA_DIT_ERR_BAD_SHAPE;
-    }
-    return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH;
+    void *kargs[] = {&p};
+    const hipError_t launched = hipLaunchKernel(g.fn, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z),
+                                                dim3(64 * g.shape.waves), kargs, (size_t)g.shape.lds_bytes, reinterpret_cast<hipStream_t>(stream));
+    return hipGetLastError() == hipSuccess && launched == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH;
 }

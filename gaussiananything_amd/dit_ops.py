@@ -24,6 +24,15 @@ class GaGemmArgs(ctypes.Structure):
                 ("splitk_ws", c_p), ("splitk_ws_bytes", i64)]
 
 
+class GaGemmPlan(ctypes.Structure):
+    """include/ga_dit.h: GaGemmPlan (what ga_gemm_bf16 launches; ga_gemm_plan / ga_gemm_instances)"""
+    _fields_ = [(n, i32) for n in ("family", "epilogue", "tile_m", "tile_n", "waves", "slots", "rem", "mt", "splits", "grid_x",
+                                   "grid_y", "grid_z", "xmap", "wt", "lds_bytes")]
+
+
+GEMM_FAMILY_GENERAL, GEMM_FAMILY_RING, GEMM_FAMILY_SPLITK = 0, 1, 2
+
+
 class GaAttentionArgs(ctypes.Structure):
     _fields_ = [("batch", i32), ("heads", i32), ("Lq", i32), ("Lk", i32), ("q", c_p), ("k", c_p), ("vt", c_p),
                 ("q_stride", i64), ("k_stride", i64), ("vt_ld", i64), ("q_norm_weight", c_p), ("k_norm_weight", c_p),
@@ -91,7 +100,7 @@ class GaDitForwardArgs(ctypes.Structure):
 
 DIT_EXPORTS = ("ga_gemm_bf16", "ga_attention_bf16", "ga_attention_hd_bf16", "ga_head_rmsnorm_bf16", "ga_rmsnorm_modulate", "ga_small_linear", "ga_dit_workspace_bytes",
                "ga_dit_cache_context", "ga_dit_forward", "ga_dit_pooled_vector", "ga_dit_shift_bias", "ga_dit_sampler_advance", "ga_ode_dopri5_stage", "ga_ode_dopri5_finish",
-               "ga_dit_version", "ga_gemm_splitk_workspace_bytes", "ga_gemm_splitk_mode")
+               "ga_dit_version", "ga_gemm_splitk_workspace_bytes", "ga_gemm_splitk_mode", "ga_gemm_plan", "ga_gemm_instances")
 _ERR = {-1: "GA_DIT_ERR_NULL_ARG", -2: "GA_DIT_ERR_BAD_SHAPE", -4: "GA_DIT_ERR_LAUNCH"}
 _bound = False
 
@@ -128,6 +137,10 @@ def lib():
         L.ga_gemm_splitk_workspace_bytes.argtypes = [i32, i32]
         L.ga_gemm_splitk_mode.restype = ctypes.c_int
         L.ga_gemm_splitk_mode.argtypes = [ctypes.c_int]
+        L.ga_gemm_plan.restype = ctypes.c_int
+        L.ga_gemm_plan.argtypes = [ctypes.POINTER(GaGemmArgs), ctypes.POINTER(GaGemmPlan)]
+        L.ga_gemm_instances.restype = ctypes.c_int
+        L.ga_gemm_instances.argtypes = [ctypes.POINTER(GaGemmPlan), i32]
         _bound = True
     return L
 
@@ -179,6 +192,21 @@ def gemm(A, W, bias=None, epilogue=EPI_STORE_BF16, out=None, gate=None, rows_per
                    _ptr(splitk_ws), splitk_ws.numel() if splitk_ws is not None else 0)
     check(lib().ga_gemm_bf16(ctypes.byref(a), _stream(A)), "ga_gemm_bf16")
     return out
+
+
+def gemm_plan(args):
+    """GaGemmArgs -> the GaGemmPlan ga_gemm_bf16 would launch for it in this process (no GPU needed; raises on invalid arguments)"""
+    plan = GaGemmPlan()
+    check(lib().ga_gemm_plan(ctypes.byref(args), ctypes.byref(plan)), "ga_gemm_plan")
+    return plan
+
+
+def gemm_instances():
+    """every (kernel instance, epilogue) the library is built with, as GaGemmPlan records without a grid"""
+    n = lib().ga_gemm_instances(None, 0)
+    out = (GaGemmPlan * n)()
+    lib().ga_gemm_instances(out, n)
+    return list(out)
 
 
 def splitk_workspace(M, N, device):

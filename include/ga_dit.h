@@ -123,6 +123,31 @@ int ga_gemm_splitk_mode(int mode);
 
 int ga_gemm_bf16(const GaGemmArgs *args, void *stream);
 
+/* What ga_gemm_bf16 launches for `args` in this process (its environment switches and ga_gemm_splitk_mode included): the launch
+ * itself is taken from this plan.  No HIP call -- answers on a machine without a GPU; pointers are checked for NULL and alignment
+ * only, never dereferenced.  Returns the error code ga_gemm_bf16 would return for these arguments, or 0 and fills *plan. */
+#define GA_GEMM_FAMILY_GENERAL 0  /* gemm_bf16_kernel: 128 columns x 32 MT rows, 4 waves                                       */
+#define GA_GEMM_FAMILY_RING 1     /* gemm_ring_kernel: 192 x 128 (8 waves), 96 x 128, 96 x 64, 64 x 64 (4 waves)               */
+#define GA_GEMM_FAMILY_SPLITK 2   /* gemm_ring_kernel with `splits` workgroups per output tile (GaGemmArgs.splitk_ws)           */
+typedef struct GaGemmPlan {
+    int32_t family;           /* GA_GEMM_FAMILY_*                                                    */
+    int32_t epilogue;         /* GA_GEMM_EPI_* of the instance                                       */
+    int32_t tile_m, tile_n;   /* output rows x columns of a workgroup tile                           */
+    int32_t waves;            /* waves per workgroup (64 lanes each)                                 */
+    int32_t slots;            /* LDS ring slots (K-tiles of 64)                                      */
+    int32_t rem;              /* ring: K-tiles past a multiple of `slots` in the peeled tail         */
+    int32_t mt;               /* general: 16-row fragments per wave (tile_m = 32 mt); 0 otherwise    */
+    int32_t splits;           /* split-K: workgroups per output tile (= grid_z); 1 otherwise         */
+    int32_t grid_x, grid_y, grid_z;
+    int32_t xmap;             /* tile -> XCD blocking of the ring kernels                            */
+    int32_t wt;               /* write-through output stores                                         */
+    int32_t lds_bytes;        /* dynamic LDS per workgroup                                           */
+} GaGemmPlan;
+int ga_gemm_plan(const GaGemmArgs *args, GaGemmPlan *plan);
+/* Every (kernel instance, epilogue) ga_gemm_bf16 is built with, from the table its launch is looked up in: fills up to `capacity`
+ * entries (grid_* and the per-call fields xmap / wt zero) and returns how many there are. */
+int ga_gemm_instances(GaGemmPlan *out, int32_t capacity);
+
 /* out[b][n] = bias[n] + sum_k shift[b * shift_stride + k] * W[n][k]  (fp32; W [N, K] bf16, row-major or the tiled image; N % 8 == 0,
  * K % 64 == 0; bias may be NULL): the per-batch bias row of a consumer GEMM behind a folded modulated RMSNorm (GaGemmArgs.bias_stride).
  * ga_dit_forward computes these rows for every block's qkv and fc1 projection in one launch per evaluation. */
