@@ -594,19 +594,79 @@ __global__ __launch_bounds__(NW * KS * 64) void attention_fwd_kernel(GaAttention
     }
 }
 
-template <int NW, int KS>
-static void launch_attention(const GaAttentionArgs &a, hipStream_t s, const ShiftBiasJob *job, const PrefetchJob *pf = nullptr, int pf_wgs = 0)
+// The ONE place the configuration is chosen: the launch (dispatch_attention), the plan query (ga_attention_plan) and what ga_dit_forward
+// asks about a launch before it makes it (attention_workgroups, attention_fuses_q) all read it here.
+//   128-query workgroups when they fill the chip; otherwise (the conditional half of a CFG pair alone in the image cross-attention:
+//   6 x 16 x 1 = 96 workgroups for 256 CUs) 64-query workgroups with key groups -- measured on MI355X, B = 1, 16 heads, 768 x 1369:
+//   20.7 -> 15.0 us; B = 2: 22.3 us (<8,1>) vs 28.5 us (<4,2>).
+//   Round 3 (tools/attn_cfg_sweep.py): three key groups on the small grids (1 x 16 x 768 x 1369: 15.9 -> 14.2 us, x 768 keys
+//   10.1 -> 9.6 us), and two key groups beside eight query waves while 128-query workgroups are fewer than two per CU
+//   (2 x 16 x 768 x 768: 13.7 -> 12.8 us; 4 x 16 x 768 x 1369: 39.5 -> 37.1 us); one group on the grids beyond that.
+//   K normalised while it is staged (not on the DiT path, which normalises K once per conditioning tensor): ONE instantiation, eight
+//   query waves and a single key group -- <8,2,true> / <4,3,true> spilt registers and <4,1,true> carried a private segment (round-3 review)
+struct AttnConfig {
+    int nw, ks, knorm, tps, tuned;   // tuned: the configuration came from GA_ATTN_CFG (tuning builds only)
+};
+static constexpr int kAttnInstances = 4;
+static constexpr AttnConfig g_attn_instances[kAttnInstances] = {{4, 3, 0, 1, 0}, {8, 2, 0, 1, 0}, {8, 1, 0, 2, 0}, {8, 1, 1, 1, 0}};
+
+static AttnConfig attention_config(const GaAttentionArgs *a)
 {
-    // K normalised while it is staged (not on the DiT path, which normalises K once per conditioning tensor): ONE instantiation, eight
-    // query waves and a single key group -- <8,2,true> / <4,3,true> spilt registers and <4,1,true> carried a private segment (round-3 review)
-    constexpr int QW = 8;
-    const bool knorm = a.k_norm_weight != nullptr;
-    const int rows = (knorm ? QW : NW) * 16;
-#if GA_ATTN_HEAD_MAJOR
-    dim3 grid(a.heads * a.batch, (a.Lq + rows - 1) / rows, 1);
-#else
-    dim3 grid((a.Lq + rows - 1) / rows, a.heads, a.batch);
+    AttnConfig c{};
+    const int64_t wgs128 = (int64_t)((a->Lq + 127) / 128) * a->heads * a->batch;
+    if (wgs128 <= 128) { c.nw = 4; c.ks = 3; }
+    else if (wgs128 <= 512) { c.nw = 8; c.ks = 2; }
+    else { c.nw = 8; c.ks = 1; }
+#ifdef GA_TUNING  // tuning builds only: NW*10 + KS from the environment
+    const int cfg = [] { const char *e = getenv("GA_ATTN_CFG"); return e ? atoi(e) : 0; }();   // (read per call: tools/attn_cfg_sweep.py changes it)
+    if (cfg == 23 || cfg == 43 || cfg == 22 || cfg == 41 || cfg == 82 || cfg == 21 || cfg == 42 || cfg == 81) { c.nw = cfg / 10; c.ks = cfg % 10; c.tuned = 1; }
 #endif
+    if (a->k_norm_weight) { c.nw = 8; c.ks = 1; c.knorm = 1; }
+    c.tps = (!c.knorm && c.ks == 1) ? 2 : 1;       // (the kernel's own TPS)
+    return c;
+}
+
+static void fill_attention_plan(const AttnConfig &c, const GaAttentionArgs *a, GaAttentionPlan *pl)
+{
+    *pl = GaAttentionPlan{};
+    pl->nw = c.nw; pl->ks = c.ks; pl->knorm = c.knorm; pl->tps = c.tps;
+    pl->queries_per_wg = 16 * c.nw;
+    pl->lds_bytes = c.ks * 6 * c.tps * TILE * (int)sizeof(uint16_t);
+    if (!a) return;
+    pl->fuses_q = a->qp_a != nullptr;
+    const int qt = (a->Lq + pl->queries_per_wg - 1) / pl->queries_per_wg;
+#if GA_ATTN_HEAD_MAJOR
+    pl->grid_x = a->heads * a->batch; pl->grid_y = qt; pl->grid_z = 1;
+#else
+    pl->grid_x = qt; pl->grid_y = a->heads; pl->grid_z = a->batch;
+#endif
+}
+
+// argument validation + the configuration: what ga_attention_bf16 returns before it launches
+static int attention_plan(const GaAttentionArgs *a, GaAttentionPlan *pl)
+{
+    if (!a || (!a->q && !a->qp_a) || !a->k || !a->vt || !a->out) return GA_DIT_ERR_NULL_ARG;
+    if (a->qp_a) {   // the q projection inside the workgroup: LDS-DMA path only, 16-byte aligned operands, K in 64-wide slices
+        if (!a->qp_w || a->k_norm_weight) return GA_DIT_ERR_NULL_ARG;
+        if (a->qp_k < 64 || a->qp_k % 64 || a->qp_lda % 8 || a->qp_lda < a->qp_k || ((uintptr_t)a->qp_a | (uintptr_t)a->qp_w) % 16 != 0 ||
+            (a->qp_row_ss && (a->qp_row_ss_tiles <= 0 || a->qp_row_ss_tiles % 4 != 0 || a->qp_row_ss_dim <= 0 || (uintptr_t)a->qp_row_ss % 16 != 0)))
+            return GA_DIT_ERR_BAD_SHAPE;
+    }
+    if (a->batch <= 0 || a->heads <= 0 || a->Lq <= 0 || a->Lk <= 0 || a->q_stride % 8 || a->k_stride % 8 || a->vt_ld % 8 ||
+        a->vt_ld < ((a->Lk + KB - 1) / KB) * KB || a->out_stride % 4)
+        return GA_DIT_ERR_BAD_SHAPE;
+    // 16-byte accesses (vector loads of q, LDS-DMA of k / vt, 8-byte stores of out)
+    if (((a->qp_a ? 0 : (uintptr_t)a->q) | (uintptr_t)a->k | (uintptr_t)a->vt) % 16 != 0 || (uintptr_t)a->out % 8 != 0) return GA_DIT_ERR_BAD_SHAPE;
+    const AttnConfig c = attention_config(a);
+    if (a->qp_a && (c.tuned || c.nw != 4 || c.ks != 3)) return GA_DIT_ERR_BAD_SHAPE;   // only the 64-query configuration projects q itself (attention_fuses_q)
+    fill_attention_plan(c, a, pl);
+    return GA_DIT_OK;
+}
+
+template <int NW, int KS, bool KNORM>
+static void launch_attention(const GaAttentionArgs &a, const GaAttentionPlan &pl, hipStream_t s, const ShiftBiasJob *job, const PrefetchJob *pf, int pf_wgs)
+{
+    dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
     AttnTail tail{};
     if (pf && pf_wgs > 0) { tail.pf = *pf; tail.pf_on = 1; } else pf_wgs = 0;
     if (job || pf_wgs) {
@@ -622,8 +682,7 @@ static void launch_attention(const GaAttentionArgs &a, hipStream_t s, const Shif
         tail.nwgs = (int)(grid.z - tail.y0) * per_slice;
 #endif
     }
-    if (knorm) hipLaunchKernelGGL((attention_fwd_kernel<QW, 1, true>), grid, dim3(QW * 64), 0, s, a, tail);
-    else hipLaunchKernelGGL((attention_fwd_kernel<NW, KS, false>), grid, dim3(NW * KS * 64), 0, s, a, tail);
+    hipLaunchKernelGGL((attention_fwd_kernel<NW, KS, KNORM>), grid, dim3(NW * KS * 64), 0, s, a, tail);
 }
 
 }  // namespace gadit
@@ -637,18 +696,22 @@ extern "C" int ga_attn_debug_stamps(unsigned long long *out)
 
 namespace gadit {
 static int dispatch_attention(const GaAttentionArgs *a, const ShiftBiasJob *job, void *stream, const PrefetchJob *pf = nullptr, int pf_wgs = 0);
-// workgroups of the launch dispatch_attention picks for this shape (no k-norm): a tail only pays while they leave CUs idle
+// workgroups of the launch dispatch_attention makes for this shape (pointers not looked at, k_norm_weight apart): a tail only pays
+// while they leave CUs idle
 int attention_workgroups(const GaAttentionArgs *a)
 {
-    const int64_t wgs128 = (int64_t)((a->Lq + 127) / 128) * a->heads * a->batch;
-    return (int)(wgs128 <= 128 ? (int64_t)((a->Lq + 63) / 64) * a->heads * a->batch : wgs128);
+    GaAttentionPlan pl;
+    fill_attention_plan(attention_config(a), a, &pl);
+    return (int)std::min<int64_t>((int64_t)pl.grid_x * pl.grid_y * pl.grid_z, INT32_MAX);
 }
 // the q projection can ride inside the attention workgroups (GaAttentionArgs.qp_*) when the launch takes the 64-query configuration
 bool attention_fuses_q(const GaAttentionArgs *a)
 {
-    return (int64_t)((a->Lq + 127) / 128) * a->heads * a->batch <= 128;
+    const AttnConfig c = attention_config(a);
+    return !c.tuned && !c.knorm && c.nw == 4 && c.ks == 3;
 }
-int attention_with_tail(const GaAttentionArgs *a, const ShiftBiasJob *job, void *stream, const PrefetchJob *pf, int pf_wgs)
+// the checks on tail jobs both attention files make before a launch carries one
+int attention_tail_check(const ShiftBiasJob *job, const PrefetchJob *pf)
 {
     if (job) {
         if (!job->W[0] || !job->W[1] || !job->shift || !job->out) return GA_DIT_ERR_NULL_ARG;
@@ -657,53 +720,53 @@ int attention_with_tail(const GaAttentionArgs *a, const ShiftBiasJob *job, void 
     if (pf)
         for (int r = 0; r < kPfRanges; ++r)
             if (pf->ptr[r] && pf->bytes[r] % 1024) return GA_DIT_ERR_BAD_SHAPE;
+    return GA_DIT_OK;
+}
+int attention_with_tail(const GaAttentionArgs *a, const ShiftBiasJob *job, void *stream, const PrefetchJob *pf, int pf_wgs)
+{
+    const int rc = attention_tail_check(job, pf);
+    if (rc != GA_DIT_OK) return rc;
     return dispatch_attention(a, job, stream, pf, pf_wgs);
 }
 }  // namespace gadit
 
 extern "C" int ga_attention_bf16(const GaAttentionArgs *a, void *stream) { return gadit::dispatch_attention(a, nullptr, stream); }
 
+extern "C" int ga_attention_plan(const GaAttentionArgs *a, GaAttentionPlan *plan)
+{
+    if (!plan) return GA_DIT_ERR_NULL_ARG;
+    GaAttentionPlan pl;
+    const int rc = gadit::attention_plan(a, &pl);
+    if (rc == GA_DIT_OK) *plan = pl;
+    return rc;
+}
+
+extern "C" int ga_attention_instances(GaAttentionPlan *out, int32_t capacity)
+{
+    using namespace gadit;
+    for (int i = 0; out && i < kAttnInstances && i < capacity; ++i) fill_attention_plan(g_attn_instances[i], nullptr, &out[i]);
+    return kAttnInstances;
+}
+
 static int gadit::dispatch_attention(const GaAttentionArgs *a, const ShiftBiasJob *job, void *stream, const PrefetchJob *pf, int pf_wgs)
 {
     using namespace gadit;
-    if (!a || (!a->q && !a->qp_a) || !a->k || !a->vt || !a->out) return GA_DIT_ERR_NULL_ARG;
-    if (a->qp_a) {   // the q projection inside the workgroup: LDS-DMA path only, 16-byte aligned operands, K in 64-wide slices
-        if (!a->qp_w || a->k_norm_weight) return GA_DIT_ERR_NULL_ARG;
-        if (a->qp_k < 64 || a->qp_k % 64 || a->qp_lda % 8 || a->qp_lda < a->qp_k || ((uintptr_t)a->qp_a | (uintptr_t)a->qp_w) % 16 != 0 ||
-            (a->qp_row_ss && (a->qp_row_ss_tiles <= 0 || a->qp_row_ss_tiles % 4 != 0 || a->qp_row_ss_dim <= 0 || (uintptr_t)a->qp_row_ss % 16 != 0)))
-            return GA_DIT_ERR_BAD_SHAPE;
-    }
-    if (a->batch <= 0 || a->heads <= 0 || a->Lq <= 0 || a->Lk <= 0 || a->q_stride % 8 || a->k_stride % 8 || a->vt_ld % 8 ||
-        a->vt_ld < ((a->Lk + KB - 1) / KB) * KB || a->out_stride % 4)
-        return GA_DIT_ERR_BAD_SHAPE;
-    // 16-byte accesses (vector loads of q, LDS-DMA of k / vt, 8-byte stores of out)
-    if (((a->qp_a ? 0 : (uintptr_t)a->q) | (uintptr_t)a->k | (uintptr_t)a->vt) % 16 != 0 || (uintptr_t)a->out % 8 != 0) return GA_DIT_ERR_BAD_SHAPE;
+    GaAttentionPlan pl;
+    const int rc = attention_plan(a, &pl);
+    if (rc != GA_DIT_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    // 128-query workgroups when they fill the chip; otherwise (the conditional half of a CFG pair alone in the image
-    // cross-attention: 6 x 16 x 1 = 96 workgroups for 256 CUs) 64-query workgroups with two key groups -- measured on
-    // MI355X, B = 1, 16 heads, 768 x 1369: 20.7 -> 15.0 us; B = 2: 22.3 us (<8,1>) vs 28.5 us (<4,2>).
-#ifdef GA_TUNING  // tuning builds only: NW*10 + KS from the environment
-    const int cfg = [] { const char *e = getenv("GA_ATTN_CFG"); return e ? atoi(e) : 0; }();
-#else
-    constexpr int cfg = 0;
-#endif
-    const int64_t wgs128 = (int64_t)((a->Lq + 127) / 128) * a->heads * a->batch;
-    if (a->qp_a && (cfg != 0 || wgs128 > 128)) return GA_DIT_ERR_BAD_SHAPE;   // only the 64-query configuration projects q itself (attention_fuses_q)
+    const int key = pl.nw * 10 + pl.ks;
+    if (pl.knorm) launch_attention<8, 1, true>(*a, pl, s, job, pf, pf_wgs);
+    else if (key == 43) launch_attention<4, 3, false>(*a, pl, s, job, pf, pf_wgs);
+    else if (key == 82) launch_attention<8, 2, false>(*a, pl, s, job, pf, pf_wgs);
+    else if (key == 81) launch_attention<8, 1, false>(*a, pl, s, job, pf, pf_wgs);
 #ifdef GA_TUNING
-    if (cfg == 23) { launch_attention<2, 3>(*a, s, job, pf, pf_wgs); return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH; }
-    if (cfg == 43) { launch_attention<4, 3>(*a, s, job, pf, pf_wgs); return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH; }
-    if (cfg == 22) { launch_attention<2, 2>(*a, s, job, pf, pf_wgs); return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH; }
-    if (cfg == 41) { launch_attention<4, 1>(*a, s, job, pf, pf_wgs); return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH; }
-    if (cfg == 82) { launch_attention<8, 2>(*a, s, job, pf, pf_wgs); return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH; }
-    if (cfg == 21) { launch_attention<2, 1>(*a, s, job, pf, pf_wgs); return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH; }
+    else if (key == 23) launch_attention<2, 3, false>(*a, pl, s, job, pf, pf_wgs);
+    else if (key == 22) launch_attention<2, 2, false>(*a, pl, s, job, pf, pf_wgs);
+    else if (key == 41) launch_attention<4, 1, false>(*a, pl, s, job, pf, pf_wgs);
+    else if (key == 21) launch_attention<2, 1, false>(*a, pl, s, job, pf, pf_wgs);
+    else if (key == 42) launch_attention<4, 2, false>(*a, pl, s, job, pf, pf_wgs);
 #endif
-    // Round 3 (tools/attn_cfg_sweep.py): three key groups on the small grids (1 x 16 x 768 x 1369: 15.9 -> 14.2 us, x 768 keys
-    // 10.1 -> 9.6 us), and two key groups beside eight query waves while 128-query workgroups are fewer than two per CU
-    // (2 x 16 x 768 x 768: 13.7 -> 12.8 us; 4 x 16 x 768 x 1369: 39.5 -> 37.1 us); one group on the grids beyond that.
-    if (cfg == 42) launch_attention<4, 2>(*a, s, job, pf, pf_wgs);
-    else if (cfg == 81) launch_attention<8, 1>(*a, s, job, pf, pf_wgs);
-    else if (wgs128 <= 128) launch_attention<4, 3>(*a, s, job, pf, pf_wgs);
-    else if (wgs128 <= 512) launch_attention<8, 2>(*a, s, job, pf, pf_wgs);
-    else launch_attention<8, 1>(*a, s, job, pf, pf_wgs);
+    else return GA_DIT_ERR_LAUNCH;        // (a configuration without an instance: a bug in attention_config, tests/test_attention_plan.py)
     return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH;
 }

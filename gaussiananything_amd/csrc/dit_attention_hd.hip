@@ -11,6 +11,8 @@
 // (ga_head_rmsnorm_bf16 below: the GEMM epilogue's per-head norm is 64-wide as well).
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include <type_traits>
 
 #include "dit_common.h"
@@ -478,29 +480,65 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 2)))
     }
 }
 
+// The ONE place the V^T variant's configuration is chosen: the launch (launch_hdv), the plan query (ga_attention_hd_plan) and what
+// ga_dit_forward asks about a launch before it makes it (attention_hd_workgroups, attention_hd_hosts_shift_bias) all read it here.
+// configurations: 1 = 4 waves x 16 queries (64-query workgroups), 2 = 4 waves x 32 (128), 3 = 8 waves x 16 (128: two waves per SIMD
+// hide each other's LDS / exponent latencies), 4 = two key groups of 4 waves x 16 (64).  GA_ATTN_HD_QF = 1 .. 4 forces one (A/B aid, read
+// once per process; other values are ignored).
+// same-box (tools/attn_hd_bench.py, 16 heads of 72; us for configurations 1 | 2 | 3 | 4): a CFG pair's self-attention 23.4 | 25.2 | 21.4 | 27.2,
+// one sample's cross-attention 27.9 | 40.3 | 33.6 | 21.6, one sample's self-attention 17.5 | 24.7 | 20.5 | 14.6 -- one wave per SIMD runs its
+// phases back to back, two overlap; below a round of 128-query workgroups the 64-query ones fill more CUs, and two key groups give each
+// SIMD its second wave and halve the tiles a wave walks
+struct HdvConfig {
+    int cfg, qf, nw, ks, forced;
+};
+static HdvConfig hdv_config_of(int cfg, int forced)
+{
+    switch (cfg) {
+    case 2: return HdvConfig{2, 2, 4, 1, forced};
+    case 3: return HdvConfig{3, 1, 8, 1, forced};
+    case 4: return HdvConfig{4, 1, 8, 2, forced};
+    default: return HdvConfig{1, 1, 4, 1, forced};
+    }
+}
+static HdvConfig hdv_config(const GaAttentionHdArgs *a)
+{
+    static const int qf_env = [] { const char *e = getenv("GA_ATTN_HD_QF"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 4 ? v : 0; }();
+    const long long wg128 = (long long)a->batch * a->heads * ((a->Lq + 127) / 128);
+    return hdv_config_of(qf_env ? qf_env : (wg128 >= 160 ? 3 : 4), qf_env != 0);
+}
+static size_t hdv_lds_bytes(int hd16, int ks) { return (size_t)ks * (size_t)(2 * 64 * (hd16 * 16 + 8) + 2 * hd16 * 16 * 72) * 2; }
+
+static void fill_hdv_plan(const HdvConfig &c, int hd16, const GaAttentionHdArgs *a, GaAttentionHdPlan *pl)
+{
+    *pl = GaAttentionHdPlan{};
+    pl->family = GA_ATTN_HD_FAMILY_HDV; pl->hd16 = hd16; pl->config = c.cfg; pl->qf = c.qf; pl->nw = c.nw; pl->ks = c.ks; pl->forced = c.forced;
+    pl->queries_per_wg = 16 * c.qf * c.nw / c.ks;
+    pl->lds_bytes = (int)hdv_lds_bytes(hd16, c.ks);
+    if (!a) return;
+    pl->grid_x = a->batch * a->heads; pl->grid_y = (a->Lq + pl->queries_per_wg - 1) / pl->queries_per_wg; pl->grid_z = 1;
+}
+static void fill_hd_plan(int hdp, const GaAttentionHdArgs *a, GaAttentionHdPlan *pl)
+{
+    *pl = GaAttentionHdPlan{};
+    pl->family = GA_ATTN_HD_FAMILY_HD; pl->hdp = hdp; pl->qf = 1; pl->nw = 4; pl->ks = 1; pl->queries_per_wg = 64;
+    pl->lds_bytes = (64 * (hdp + 8) + hdp * 72) * 2;
+    if (!a) return;
+    pl->grid_x = (a->Lq + 63) / 64; pl->grid_y = a->heads; pl->grid_z = a->batch;
+}
+
 template <int HD16>
-static int launch_hdv(const GaAttentionHdArgs &a, hipStream_t s, const PrefetchJob *pf, int pf_wgs, const ShiftBiasJob *job)
+static int launch_hdv(const GaAttentionHdArgs &a, const GaAttentionHdPlan &pl, hipStream_t s, const PrefetchJob *pf, int pf_wgs, const ShiftBiasJob *job)
 {
     static_assert((size_t)(2 * 64 * (HD16 * 16 + 8) + 2 * HD16 * 16 * 72) * 2 >= kSbLdsFloats * sizeof(float) || HD16 < 2, "the tail's partial sums fit the tile buffers");
-    constexpr size_t lds = (size_t)(2 * 64 * (HD16 * 16 + 8) + 2 * HD16 * 16 * 72) * 2;
-    // configurations: 1 = 4 waves x 16 queries (64-query workgroups), 2 = 4 waves x 32 (128), 3 = 8 waves x 16 (128: two waves per SIMD
-    // hide each other's LDS / exponent latencies), 4 = two key groups of 4 waves x 16 (64).  GA_ATTN_HD_QF forces one (A/B aid)
-    static const int qf_env = [] { const char *e = getenv("GA_ATTN_HD_QF"); return e ? atoi(e) : 0; }();
-    const long long wg128 = (long long)a.batch * a.heads * ((a.Lq + 127) / 128);
-    // same-box (tools/attn_hd_bench.py, 16 heads of 72; us for configurations 1 | 2 | 3 | 4): a CFG pair's self-attention 23.4 | 25.2 | 21.4 | 27.2,
-    // one sample's cross-attention 27.9 | 40.3 | 33.6 | 21.6, one sample's self-attention 17.5 | 24.7 | 20.5 | 14.6 -- one wave per SIMD runs its
-    // phases back to back, two overlap; below a round of 128-query workgroups the 64-query ones fill more CUs, and two key groups give each
-    // SIMD its second wave and halve the tiles a wave walks
-    const int cfg = qf_env ? qf_env : (wg128 >= 160 ? 3 : 4);
-    const int qpw = (cfg == 1 || cfg == 4) ? 64 : 128;
-    dim3 grid((unsigned)(a.batch * a.heads), (unsigned)((a.Lq + qpw - 1) / qpw));
+    const size_t lds = hdv_lds_bytes(HD16, 1);
+    dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
     HdTail tail{};
     tail.y0 = (int)grid.y;
     if (pf && pf_wgs > 0) { tail.pf = *pf; tail.nwgs = pf_wgs; }
     if (job) {
         // the job's waves each own K / 64 / waves K-tiles, at most kSbTilesPerWave (dit_common.h); its partial sums live in the tile buffers
-        const int waves = cfg == 3 || cfg == 4 ? 8 : 4;
-        if (job->K / 64 > kSbTilesPerWave * waves || lds < kSbLdsFloats * sizeof(float)) return GA_DIT_ERR_BAD_SHAPE;
+        if (job->K / 64 > kSbTilesPerWave * pl.nw || lds < kSbLdsFloats * sizeof(float)) return GA_DIT_ERR_BAD_SHAPE;
         tail.job = *job; tail.sb_wgs = shift_bias_wgs(job->N0, job->N1);
     }
     if (tail.nwgs + tail.sb_wgs > 0) grid.y += (unsigned)((tail.nwgs + tail.sb_wgs + (int)grid.x - 1) / (int)grid.x);
@@ -509,9 +547,9 @@ static int launch_hdv(const GaAttentionHdArgs &a, hipStream_t s, const PrefetchJ
         if (KSV * lds > 65536 && hipFuncSetAttribute((const void *)attention_hdv_kernel<HD16, QFV, NWV, KSV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(KSV * lds)) != hipSuccess) return GA_DIT_ERR_LAUNCH; \
         hipLaunchKernelGGL((attention_hdv_kernel<HD16, QFV, NWV, KSV>), grid, dim3(64 * NWV), KSV * lds, s, a, tail);              \
     } while (0)
-    if (cfg == 2) GA_HDV_LAUNCH(2, 4, 1);
-    else if (cfg == 3) GA_HDV_LAUNCH(1, 8, 1);
-    else if (cfg == 4) GA_HDV_LAUNCH(1, 8, 2);
+    if (pl.config == 2) GA_HDV_LAUNCH(2, 4, 1);
+    else if (pl.config == 3) GA_HDV_LAUNCH(1, 8, 1);
+    else if (pl.config == 4) GA_HDV_LAUNCH(1, 8, 2);
     else GA_HDV_LAUNCH(1, 4, 1);
 #undef GA_HDV_LAUNCH
     return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH;
@@ -538,31 +576,10 @@ __global__ __launch_bounds__(256) void head_rmsnorm_kernel(uint16_t *__restrict_
 
 namespace gadit {
 static int attention_hd_dispatch(const GaAttentionHdArgs *a, void *stream, const PrefetchJob *pf, int pf_wgs, const ShiftBiasJob *job);
-// the V^T variant with tail workgroups (ga_dit_forward); attention_hd_workgroups: the grid without them
-int attention_hd_with_tail(const GaAttentionHdArgs *a, void *stream, const PrefetchJob *pf, int pf_wgs, const ShiftBiasJob *job)
-{
-    return attention_hd_dispatch(a, stream, pf, pf_wgs, job);
-}
-// can a tail of this launch host a ShiftBiasJob over K columns?  (eight-wave configurations only: the launcher's own choice unless forced)
-bool attention_hd_hosts_shift_bias(const GaAttentionHdArgs *a, int K)
-{
-    static const int qf_env = [] { const char *e = getenv("GA_ATTN_HD_QF"); return e ? atoi(e) : 0; }();
-    const int waves = (qf_env == 1 || qf_env == 2) ? 4 : 8;
-    const size_t lds = (size_t)(2 * 64 * ((a->head_dim + 15) / 16 * 16 + 8) + 2 * ((a->head_dim + 15) / 16 * 16) * 72) * 2;
-    return K / 64 <= kSbTilesPerWave * waves && lds >= kSbLdsFloats * sizeof(float);
-}
-int attention_hd_workgroups(const GaAttentionHdArgs *a)
-{
-    const long long wg128 = (long long)a->batch * a->heads * ((a->Lq + 127) / 128);
-    return (int)(wg128 >= 160 ? wg128 : (long long)a->batch * a->heads * ((a->Lq + 63) / 64));
-}
-}  // namespace gadit
 
-extern "C" int ga_attention_hd_bf16(const GaAttentionHdArgs *a, void *stream) { return gadit::attention_hd_dispatch(a, stream, nullptr, 0, nullptr); }
-
-static int gadit::attention_hd_dispatch(const GaAttentionHdArgs *a, void *stream, const PrefetchJob *pf, int pf_wgs, const ShiftBiasJob *job)
+// argument validation + the instance: what ga_attention_hd_bf16 returns before it launches
+static int attention_hd_plan(const GaAttentionHdArgs *a, GaAttentionHdPlan *pl)
 {
-    using namespace gadit;
     if (!a || !a->q || !a->k || (!a->v && !a->vt) || !a->out) return GA_DIT_ERR_NULL_ARG;
     if (a->batch <= 0 || a->heads <= 0 || a->Lq <= 0 || a->Lk <= 0 || a->head_dim < 8 || a->head_dim > 128 || a->head_dim % 8 ||
         a->q_stride % 8 || a->k_stride % 8 || a->out_stride % 4)
@@ -572,26 +589,82 @@ static int gadit::attention_hd_dispatch(const GaAttentionHdArgs *a, void *stream
         if (a->vt_ld % 64 != 0 || a->vt_ld < (a->Lk + 63) / 64 * 64 || (uintptr_t)a->vt % 16 != 0 || (a->q_norm_weight && (uintptr_t)a->q_norm_weight % 16 != 0) ||
             (a->k_norm_weight && (uintptr_t)a->k_norm_weight % 16 != 0))
             return GA_DIT_ERR_BAD_SHAPE;
-        hipStream_t sv = reinterpret_cast<hipStream_t>(stream);
-        switch ((a->head_dim + 15) / 16) {
-        case 1: return launch_hdv<1>(*a, sv, pf, pf_wgs, job);
-        case 2: return launch_hdv<2>(*a, sv, pf, pf_wgs, job);
-        case 3: return launch_hdv<3>(*a, sv, pf, pf_wgs, job);
-        case 4: return launch_hdv<4>(*a, sv, pf, pf_wgs, job);
-        case 5: return launch_hdv<5>(*a, sv, pf, pf_wgs, job);
-        case 6: return launch_hdv<6>(*a, sv, pf, pf_wgs, job);
-        case 7: return launch_hdv<7>(*a, sv, pf, pf_wgs, job);
-        default: return launch_hdv<8>(*a, sv, pf, pf_wgs, job);
-        }
+        fill_hdv_plan(hdv_config(a), (a->head_dim + 15) / 16, a, pl);
+        return GA_DIT_OK;
     }
     if (a->q_norm_weight || a->k_norm_weight) return GA_DIT_ERR_BAD_SHAPE;     // (the norms inside the kernel belong to the V^T variant)
     if (a->v_stride % 8 || (uintptr_t)a->v % 16 != 0) return GA_DIT_ERR_BAD_SHAPE;
-    const dim3 grid((unsigned)((a->Lq + 63) / 64), (unsigned)a->heads, (unsigned)a->batch);
+    fill_hd_plan((a->head_dim + 31) / 32 * 32, a, pl);
+    return GA_DIT_OK;
+}
+
+// the V^T variant with tail workgroups (ga_dit_forward); attention_hd_workgroups: the grid without them
+int attention_hd_with_tail(const GaAttentionHdArgs *a, void *stream, const PrefetchJob *pf, int pf_wgs, const ShiftBiasJob *job)
+{
+    const int rc = attention_tail_check(job, pf);
+    if (rc != GA_DIT_OK) return rc;
+    return attention_hd_dispatch(a, stream, pf, pf_wgs, job);
+}
+// can a tail of this launch host a ShiftBiasJob over K columns?  (the launcher's own test: enough waves, and tile buffers that hold its sums)
+bool attention_hd_hosts_shift_bias(const GaAttentionHdArgs *a, int K)
+{
+    return K / 64 <= kSbTilesPerWave * hdv_config(a).nw && hdv_lds_bytes((a->head_dim + 15) / 16, 1) >= kSbLdsFloats * sizeof(float);
+}
+int attention_hd_workgroups(const GaAttentionHdArgs *a)
+{
+    GaAttentionHdPlan pl;
+    fill_hdv_plan(hdv_config(a), (a->head_dim + 15) / 16, a, &pl);
+    return (int)std::min<long long>((long long)pl.grid_x * pl.grid_y, INT32_MAX);
+}
+}  // namespace gadit
+
+extern "C" int ga_attention_hd_bf16(const GaAttentionHdArgs *a, void *stream) { return gadit::attention_hd_dispatch(a, stream, nullptr, 0, nullptr); }
+
+extern "C" int ga_attention_hd_plan(const GaAttentionHdArgs *a, GaAttentionHdPlan *plan)
+{
+    if (!plan) return GA_DIT_ERR_NULL_ARG;
+    GaAttentionHdPlan pl;
+    const int rc = gadit::attention_hd_plan(a, &pl);
+    if (rc == GA_DIT_OK) *plan = pl;
+    return rc;
+}
+
+// hdv: HD16 = 1 .. 8 in the four configurations (1 and 2 only through GA_ATTN_HD_QF); hd: HDP = 32, 64, 96, 128
+extern "C" int ga_attention_hd_instances(GaAttentionHdPlan *out, int32_t capacity)
+{
+    using namespace gadit;
+    int n = 0;
+    for (int hd16 = 1; hd16 <= 8; ++hd16)
+        for (int cfg = 1; cfg <= 4; ++cfg, ++n)
+            if (out && n < capacity) fill_hdv_plan(hdv_config_of(cfg, cfg <= 2), hd16, nullptr, &out[n]);
+    for (int hdp = 32; hdp <= 128; hdp += 32, ++n)
+        if (out && n < capacity) fill_hd_plan(hdp, nullptr, &out[n]);
+    return n;
+}
+
+static int gadit::attention_hd_dispatch(const GaAttentionHdArgs *a, void *stream, const PrefetchJob *pf, int pf_wgs, const ShiftBiasJob *job)
+{
+    using namespace gadit;
+    GaAttentionHdPlan pl;
+    const int rc = attention_hd_plan(a, &pl);
+    if (rc != GA_DIT_OK) return rc;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int hdp = (a->head_dim + 31) / 32 * 32;
-    if (hdp == 32) hipLaunchKernelGGL(attention_hd_kernel<32>, grid, dim3(256), 0, s, *a);
-    else if (hdp == 64) hipLaunchKernelGGL(attention_hd_kernel<64>, grid, dim3(256), 0, s, *a);
-    else if (hdp == 96) hipLaunchKernelGGL(attention_hd_kernel<96>, grid, dim3(256), 0, s, *a);
+    if (pl.family == GA_ATTN_HD_FAMILY_HDV) {
+        switch (pl.hd16) {
+        case 1: return launch_hdv<1>(*a, pl, s, pf, pf_wgs, job);
+        case 2: return launch_hdv<2>(*a, pl, s, pf, pf_wgs, job);
+        case 3: return launch_hdv<3>(*a, pl, s, pf, pf_wgs, job);
+        case 4: return launch_hdv<4>(*a, pl, s, pf, pf_wgs, job);
+        case 5: return launch_hdv<5>(*a, pl, s, pf, pf_wgs, job);
+        case 6: return launch_hdv<6>(*a, pl, s, pf, pf_wgs, job);
+        case 7: return launch_hdv<7>(*a, pl, s, pf, pf_wgs, job);
+        default: return launch_hdv<8>(*a, pl, s, pf, pf_wgs, job);
+        }
+    }
+    const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y, (unsigned)pl.grid_z);
+    if (pl.hdp == 32) hipLaunchKernelGGL(attention_hd_kernel<32>, grid, dim3(256), 0, s, *a);
+    else if (pl.hdp == 64) hipLaunchKernelGGL(attention_hd_kernel<64>, grid, dim3(256), 0, s, *a);
+    else if (pl.hdp == 96) hipLaunchKernelGGL(attention_hd_kernel<96>, grid, dim3(256), 0, s, *a);
     else hipLaunchKernelGGL(attention_hd_kernel<128>, grid, dim3(256), 0, s, *a);
     return hipGetLastError() == hipSuccess ? GA_DIT_OK : GA_DIT_ERR_LAUNCH;
 }

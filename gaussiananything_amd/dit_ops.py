@@ -46,6 +46,20 @@ class GaAttentionHdArgs(ctypes.Structure):
                 ("vt", c_p), ("vt_ld", i64), ("q_norm_weight", c_p), ("k_norm_weight", c_p)]
 
 
+class GaAttentionPlan(ctypes.Structure):
+    """include/ga_dit.h: GaAttentionPlan (what ga_attention_bf16 launches; ga_attention_plan / ga_attention_instances)"""
+    _fields_ = [(n, i32) for n in ("nw", "ks", "knorm", "tps", "queries_per_wg", "fuses_q", "grid_x", "grid_y", "grid_z", "lds_bytes")]
+
+
+class GaAttentionHdPlan(ctypes.Structure):
+    """include/ga_dit.h: GaAttentionHdPlan (what ga_attention_hd_bf16 launches; ga_attention_hd_plan / ga_attention_hd_instances)"""
+    _fields_ = [(n, i32) for n in ("family", "hd16", "hdp", "config", "qf", "nw", "ks", "forced", "queries_per_wg", "grid_x", "grid_y",
+                                   "grid_z", "lds_bytes")]
+
+
+ATTN_HD_FAMILY_HDV, ATTN_HD_FAMILY_HD = 1, 2
+
+
 class GaRmsNormArgs(ctypes.Structure):
     _fields_ = [("M", i32), ("D", i32), ("rows_per_batch", i32), ("x", c_p), ("weight", c_p), ("scale", c_p),
                 ("shift", c_p), ("mod_stride", i64), ("out", c_p), ("row_bias", c_p), ("row_bias_first", i32)]
@@ -100,7 +114,8 @@ class GaDitForwardArgs(ctypes.Structure):
 
 DIT_EXPORTS = ("ga_gemm_bf16", "ga_attention_bf16", "ga_attention_hd_bf16", "ga_head_rmsnorm_bf16", "ga_rmsnorm_modulate", "ga_small_linear", "ga_dit_workspace_bytes",
                "ga_dit_cache_context", "ga_dit_forward", "ga_dit_pooled_vector", "ga_dit_shift_bias", "ga_dit_sampler_advance", "ga_ode_dopri5_stage", "ga_ode_dopri5_finish",
-               "ga_dit_version", "ga_gemm_splitk_workspace_bytes", "ga_gemm_splitk_mode", "ga_gemm_plan", "ga_gemm_instances")
+               "ga_dit_version", "ga_gemm_splitk_workspace_bytes", "ga_gemm_splitk_mode", "ga_gemm_plan", "ga_gemm_instances",
+               "ga_attention_plan", "ga_attention_instances", "ga_attention_hd_plan", "ga_attention_hd_instances")
 _ERR = {-1: "GA_DIT_ERR_NULL_ARG", -2: "GA_DIT_ERR_BAD_SHAPE", -4: "GA_DIT_ERR_LAUNCH"}
 _bound = False
 
@@ -141,6 +156,11 @@ def lib():
         L.ga_gemm_plan.argtypes = [ctypes.POINTER(GaGemmArgs), ctypes.POINTER(GaGemmPlan)]
         L.ga_gemm_instances.restype = ctypes.c_int
         L.ga_gemm_instances.argtypes = [ctypes.POINTER(GaGemmPlan), i32]
+        for fn, args_t, plan_t in (("ga_attention", GaAttentionArgs, GaAttentionPlan), ("ga_attention_hd", GaAttentionHdArgs, GaAttentionHdPlan)):
+            getattr(L, fn + "_plan").restype = ctypes.c_int
+            getattr(L, fn + "_plan").argtypes = [ctypes.POINTER(args_t), ctypes.POINTER(plan_t)]
+            getattr(L, fn + "_instances").restype = ctypes.c_int
+            getattr(L, fn + "_instances").argtypes = [ctypes.POINTER(plan_t), i32]
         _bound = True
     return L
 
@@ -206,6 +226,36 @@ def gemm_instances():
     n = lib().ga_gemm_instances(None, 0)
     out = (GaGemmPlan * n)()
     lib().ga_gemm_instances(out, n)
+    return list(out)
+
+
+def attention_plan(args):
+    """GaAttentionArgs -> the GaAttentionPlan ga_attention_bf16 would launch for it (no GPU needed; raises on invalid arguments)"""
+    plan = GaAttentionPlan()
+    check(lib().ga_attention_plan(ctypes.byref(args), ctypes.byref(plan)), "ga_attention_plan")
+    return plan
+
+
+def attention_hd_plan(args):
+    """GaAttentionHdArgs -> the GaAttentionHdPlan ga_attention_hd_bf16 would launch for it in this process (GA_ATTN_HD_QF included)"""
+    plan = GaAttentionHdPlan()
+    check(lib().ga_attention_hd_plan(ctypes.byref(args), ctypes.byref(plan)), "ga_attention_hd_plan")
+    return plan
+
+
+def attention_instances():
+    """every attention_fwd_kernel instance the library is built with, as GaAttentionPlan records without a grid"""
+    n = lib().ga_attention_instances(None, 0)
+    out = (GaAttentionPlan * n)()
+    lib().ga_attention_instances(out, n)
+    return list(out)
+
+
+def attention_hd_instances():
+    """every attention_hdv_kernel / attention_hd_kernel instance, as GaAttentionHdPlan records without a grid"""
+    n = lib().ga_attention_hd_instances(None, 0)
+    out = (GaAttentionHdPlan * n)()
+    lib().ga_attention_hd_instances(out, n)
     return list(out)
 
 

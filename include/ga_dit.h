@@ -184,6 +184,25 @@ typedef struct GaAttentionArgs {
 
 int ga_attention_bf16(const GaAttentionArgs *args, void *stream);
 
+/* What ga_attention_bf16 launches for `args`: attention_fwd_kernel<nw, ks, knorm> (dit_attention.hip); the launch itself, the tail
+ * sizing of ga_dit_forward and its decision to project q inside the workgroups are taken from this plan.  No HIP call -- answers on a
+ * machine without a GPU; pointers are checked for NULL and alignment only, never dereferenced.  Returns the error code
+ * ga_attention_bf16 would return for these arguments, or 0 and fills *plan. */
+typedef struct GaAttentionPlan {
+    int32_t nw;               /* query waves per key group, 16 query rows each                                  */
+    int32_t ks;               /* key groups: group g walks the 64-key tiles g, g + ks, ...; merged through LDS  */
+    int32_t knorm;            /* 1: K is RMS-normalised while it is staged (through registers, not LDS-DMA)     */
+    int32_t tps;              /* 64-key tiles per barrier stage (2 only for ks == 1 without knorm)              */
+    int32_t queries_per_wg;   /* 16 nw                                                                          */
+    int32_t fuses_q;          /* 1: this launch computes the q projection itself (GaAttentionArgs.qp_a)         */
+    int32_t grid_x, grid_y, grid_z;   /* the attention grid (tail workgroups of ga_dit_forward not included)    */
+    int32_t lds_bytes;        /* LDS per workgroup: ks rings of 3 slots x tps tiles of K and of V^T             */
+} GaAttentionPlan;
+int ga_attention_plan(const GaAttentionArgs *args, GaAttentionPlan *plan);
+/* Every kernel instance ga_attention_bf16 is built with (tuning builds excluded): fills up to `capacity` entries (grid_* and fuses_q
+ * zero) and returns how many there are. */
+int ga_attention_instances(GaAttentionPlan *out, int32_t capacity);
+
 /* The same attention for head dims OTHER than 64 (head_dim % 8 == 0, <= 128): DiT-PixArt-PCD-CLAY-XL of the reference registry has 16
  * heads of 72 (/root/reference/dit/dit_i23d.py:1526-1535, 1677).  q, k, v row-major: row (b, i) of q starts at q + (b*Lq + i)*q_stride +
  * h*head_dim (k, v: b*Lk + j); q and k ALREADY carry their per-head RMSNorm (ga_head_rmsnorm_bf16); softmax scale head_dim^-1/2.
@@ -206,6 +225,27 @@ typedef struct GaAttentionHdArgs {
 } GaAttentionHdArgs;
 
 int ga_attention_hd_bf16(const GaAttentionHdArgs *args, void *stream);
+
+/* What ga_attention_hd_bf16 launches for `args` in this process (GA_ATTN_HD_QF included): the launch and the tail sizing of
+ * ga_dit_forward are taken from this plan.  Host-only like ga_attention_plan; returns the launch's error code or 0. */
+#define GA_ATTN_HD_FAMILY_HDV 1   /* attention_hdv_kernel<hd16, qf, nw, ks>: the V^T variant (GaAttentionHdArgs.vt)   */
+#define GA_ATTN_HD_FAMILY_HD 2    /* attention_hd_kernel<hdp>: v row-major, 4 waves x 16 queries                      */
+typedef struct GaAttentionHdPlan {
+    int32_t family;           /* GA_ATTN_HD_FAMILY_*                                                              */
+    int32_t hd16;             /* hdv: head dim in 16-wide steps (1 .. 8); 0 otherwise                             */
+    int32_t hdp;              /* hd: head dim rounded up to 32 (32 .. 128); 0 otherwise                           */
+    int32_t config;           /* hdv: 1 = 4 waves x 16 queries, 2 = 4 x 32, 3 = 8 x 16, 4 = two key groups of 4 x 16; 0 otherwise */
+    int32_t qf;               /* 16-query fragments per wave                                                      */
+    int32_t nw;               /* waves per workgroup (all key groups)                                             */
+    int32_t ks;               /* key groups                                                                       */
+    int32_t forced;           /* plan: the configuration came from GA_ATTN_HD_QF; instance list: only that switch reaches it */
+    int32_t queries_per_wg;
+    int32_t grid_x, grid_y, grid_z;   /* the attention grid (tail workgroups not included)                        */
+    int32_t lds_bytes;        /* LDS per workgroup (hdv: dynamic)                                                 */
+} GaAttentionHdPlan;
+int ga_attention_hd_plan(const GaAttentionHdArgs *args, GaAttentionHdPlan *plan);
+/* Every kernel instance ga_attention_hd_bf16 is built with (grid_* zero); returns how many there are. */
+int ga_attention_hd_instances(GaAttentionHdPlan *out, int32_t capacity);
 
 /* In place: x[r][h][:] *= rsqrt(mean(x[r][h][:]^2) + 1e-5) * weight[:] for r < rows, h < heads (bf16 storage, fp32 arithmetic; row r starts
  * at x + r*row_stride): the per-head q / k RMSNorm of dit/norm.py:29-43 for head dims the projection GEMM's epilogue does not cover. */

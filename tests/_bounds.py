@@ -113,3 +113,145 @@ def group_sumsq(x, R):
     """fp32 sum of the squares of 64 values x_hat, |x_hat - x| <= R, over [..., G, 64]: returns (ref, bound)"""
     ref = x.pow(2).sum(-1)
     return ref, (2 * x.abs() * R + R * R).sum(-1) + gamma(64) * (x.abs() + R).pow(2).sum(-1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Attention (dit_attention.hip, dit_attention_hd.hip).  Reference: float64 softmax over the exact values the kernel reads; scores
+# in LOG2 units S_ij = c sum_d qh_id kh_jd, where qh / kh are the bf16 operands of the kernel's QK^T MFMA and c is what it applies
+# after the product (1 where the softmax scale and log2 e are folded into qh; head_dim^-1/2 log2 e in the exponent's FMA otherwise).
+#
+# 1. Operands.  qh (and kh where K is normalised in the kernel) is bf16(x_hat), x_hat the fp32 evaluation of a deterministic
+#    function x of the inputs with |x_hat - x| <= tau |x| (or <= P).  Rounding is monotone, so bf16(x_hat) lies between bf16(x - e)
+#    and bf16(x + e): the reference uses bf16(x) itself (the MIRROR) and an element may deviate by dq = max(bf16(x + e) - bf16(x),
+#    bf16(x) - bf16(x - e)) -- zero unless x is within e of a rounding boundary, one bf16 ulp there.  (bf16_round rounds float64
+#    directly: torch's double -> float -> bfloat16 would round twice.)
+# 2. Scores.  Key j of query i carries an uncertainty D_ij (log2 units) of
+#      c (dq |kh|^T + |qh| dk^T + dq dk^T)                      operands on the other side of a rounding boundary
+#    + (gamma(2 n + 4) + rel_c) (A_ij + smax_i + lazy)           A = c |qh| |kh|^T: fp32 accumulation of n products that starts at
+#                                                                 minus the reference maximum, the subtraction (or FMA) that forms the
+#                                                                 exponent, the error rel_c of the fp32 value of c; smax_i = max_j |S_ij|
+#                                                                 bounds every reference maximum, `lazy` what a score may exceed it by
+#    + gamma(T + G + 2) (2 smax_i + lazy)                        roundings of the running reference itself (m += delta once per tile at
+#                                                                 most, T tiles; m_g - m_all in the merge of G key groups): a weight is
+#                                                                 scaled by exp2 of EXACTLY the delta its reference moved by, so only
+#                                                                 these roundings make the references of two keys inconsistent
+#    and, in nats, D = ln 2 (the above) + (T + G + 2) EXP2_REL: a weight is a product of at most T + G + 1 v_exp_f32 results.
+#    The common factor 2^(m - m_hat) of a lazy or rounded reference cancels between numerator and denominator.
+# 3. Output.  The kernel sums weights p_j g_j, g_j in [e^-D_j, e^D_j] (p: exact softmax numerators, out: exact result):
+#      |sum p g v / sum p g - out| = |sum p g (v - out)| / sum p g <= sum_j p_j (e^D_j - 1) |v_j - out| / sum_j p_j e^-D_j
+#    (sum_j p_j (v_j - out) = 0 removes the g = 1 part); the bf16 rounding of P touches the numerator only: + ub sum p e^D |v| / den;
+#    fp32 accumulation of numerator and denominator over Lk terms with a rescale per tile and the merge: gamma(2 (Lk + T + G + 4))
+#    times sum p e^D |v| / den for each; 1 / l, the product, then the bf16 store.  v_exp_f32 flushes results below 2^-126 to zero,
+#    where g in [e^-D, e^D] does not hold: such a weight is below 2^(lazy - 126) of a row sum >= 1, Lk of them move the output by
+#    less than Lk 2^(lazy - 126) max|v| (FLUSH below).
+EXP2_REL = 2 * U                    # v_exp_f32: 1 ulp
+LOG2E_F32 = 1.44269502162933349609375        # the fp32 value of the kernels' literal 1.4426950408889634f
+EPS_F32 = 9.99999974737875163555145263671875e-06    # 1e-5f
+
+
+def bf16_round(x):
+    """float64 -> nearest bf16 value (ties to even), as float64; one rounding"""
+    m, e = torch.frexp(x)
+    return torch.ldexp(torch.round(m * 256.0) / 256.0, e)
+
+
+def rounded_operand(x, err):
+    """(bf16(x), dq) for a kernel value bf16(x_hat), |x_hat - x| <= err (absolute, elementwise)"""
+    ref = bf16_round(x)
+    return ref, torch.maximum(bf16_round(x + err) - ref, ref - bf16_round(x - err))
+
+
+def rms_scale_rel(n):
+    """relative error of rsqrtf(fl(fl(sum of n exact fp32 squares) / n) + eps): the sum gamma(n - 1), the division (or product with an
+    inexact 1 / n) and the addition of eps gamma(3); rsqrt halves a relative argument error; its own error RSQRT_REL"""
+    x = gamma(n + 2)
+    return (1 + x / (2 * (1 - x))) * (1 + RSQRT_REL) - 1
+
+
+def attn_q_fwd(q, wq):
+    """dit_attention.hip, q read from memory: qh = bf16(fl(fl(q w) rs)), rs = fl(C rsqrtf(mean q^2 + eps)) with C = 64^-1/2 log2 e as the
+    fp32 product 0.125f * 1.4426950408889634f (exact); without the norm qh = bf16(fl(q C)).  q [..., 64] float64 -> (qh, dq)."""
+    C = 0.125 * LOG2E_F32
+    if wq is None:
+        x, tau = q * C, gamma(1)
+    else:
+        x = q * wq * torch.rsqrt(q.pow(2).mean(-1, keepdim=True) + EPS_F32) * C
+        tau = (1 + rms_scale_rel(64)) * (1 + gamma(3)) - 1
+    return rounded_operand(x, x.abs() * tau)
+
+
+def attn_q_proj(A, W, T_sum, tiles, dim, eps, wq):
+    """dit_attention.hip, the q projection inside the workgroup: y = (A W^T) r per head, r the folded RMSNorm row scale (T_sum None:
+    none), the per-head norm (wq None: none), then qh = bf16(fl(bf16(y_hat) C)) -- two bf16 roundings.  A [rows, K], W [H, 64, K]
+    float64 -> (qh, dq) of [rows, H, 64].  Errors of y_hat from accumulation / row_scale / head_norm above (the partial sums of the key
+    groups meet in a fixed order: still one summation tree of K products)."""
+    K = A.shape[-1]
+    z = torch.einsum("rk,hdk->rhd", A, W)
+    E = accumulation(torch.einsum("rk,hdk->rhd", A.abs(), W.abs()), K)
+    if T_sum is not None:
+        r, rho = row_scale(T_sum[:, None, None], tiles, dim, eps)
+        z, E = scale_then_bias(z, E, r, rho, torch.zeros_like(z))
+    if wq is not None:
+        z, E = head_norm(z, E, wq, EPS_F32)
+    C = 0.125 * LOG2E_F32
+    t_lo, t_ref, t_hi = bf16_round(z - E), bf16_round(z), bf16_round(z + E)
+    one = gamma(1)
+    ref = bf16_round(t_ref * C)
+    lo, hi = bf16_round(t_lo * C - (t_lo * C).abs() * one), bf16_round(t_hi * C + (t_hi * C).abs() * one)
+    return ref, torch.maximum(hi - ref, ref - lo)
+
+
+def attn_rows_normed(x, w, d):
+    """bf16(fl(x fl(rs w))), rs = rsqrtf(fl(sum x^2 / d) + eps): K rows normalised while they are staged (both files) and q rows of
+    the V^T variant of dit_attention_hd.hip.  x [..., d] float64 -> (xh, dx)."""
+    y = x * w * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + EPS_F32)
+    tau = (1 + rms_scale_rel(max(d, 64))) * (1 + gamma(2)) - 1
+    return rounded_operand(y, y.abs() * tau)
+
+
+def attn_q_hd(q, d):
+    """attention_hd_kernel: qh = bf16(fl(q rs)), rs = fl(rsqrtf(d) log2 e)"""
+    x = q * (LOG2E_F32 / math.sqrt(d))
+    return rounded_operand(x, x.abs() * (RSQRT_REL + gamma(2)))
+
+
+def attention(qh, dq, kh, dk, v, c=1.0, n_acc=64, rel_c=0.0, lazy=8.0, tiles=None, groups=1, budget=1 << 27):
+    """(out, bound, dominant key) of softmax_j(S_ij ln 2) v_j, S = c qh kh^T (log2 units), by the model above.  qh, dq [P, Lq, d];
+    kh, dk [P, Lk, d]; v [P, Lk, dv] float64 (P: batch x heads); chunked over P and Lq so that the [p, q, Lk, dv] tensor of
+    |v_j - out_i| stays under `budget` elements."""
+    P, Lq, _ = qh.shape
+    Lk, dv = v.shape[1], v.shape[2]
+    T = tiles if tiles is not None else (Lk + 63) // 64
+    G = groups
+    LN2 = math.log(2.0)
+    out = torch.empty(P, Lq, dv, dtype=torch.float64, device=qh.device)
+    bound = torch.empty_like(out)
+    dom = torch.empty(P, Lq, dtype=torch.long, device=qh.device)
+    qc = max(1, min(Lq, budget // (Lk * dv)))
+    pc = max(1, min(P, budget // (qc * Lk * dv)))
+    g_acc, g_ref, g_sum = gamma(2 * n_acc + 4) + rel_c, gamma(T + G + 2), gamma(2 * (Lk + T + G + 4))
+    flush = Lk * 2.0 ** (lazy - 126)
+    for p0 in range(0, P, pc):
+        ps = slice(p0, p0 + pc)
+        kT, akT, dkT = kh[ps].transpose(1, 2), kh[ps].abs().transpose(1, 2), dk[ps].transpose(1, 2)
+        vv, av = v[ps], v[ps].abs()
+        vmax = av.amax((1, 2))[:, None, None]
+        for q0 in range(0, Lq, qc):
+            qs = slice(q0, q0 + qc)
+            q_, dq_ = qh[ps, qs], dq[ps, qs]
+            S = c * (q_ @ kT)
+            A = c * (q_.abs() @ akT)
+            smax = S.abs().amax(-1, keepdim=True)
+            D = c * (dq_ @ akT + q_.abs() @ dkT + dq_ @ dkT) + g_acc * (A + smax + lazy) + g_ref * (2 * smax + lazy)
+            D = LN2 * D + (T + G + 2) * EXP2_REL
+            m = S.amax(-1, keepdim=True)
+            p = torch.exp((S - m) * LN2)
+            o = (p @ vv) / p.sum(-1, keepdim=True)
+            den = (p * torch.exp(-D)).sum(-1, keepdim=True)
+            up = p * torch.exp(D)
+            t1 = torch.einsum("pqk,pqkd->pqd", p * torch.expm1(D), (vv[:, None] - o[:, :, None]).abs()) / den
+            num = (up @ av) / den
+            Pe = t1 + UB * num + 2 * g_sum * num + flush * vmax
+            Pe = Pe + gamma(4) * (o.abs() + Pe)
+            out[ps, qs], bound[ps, qs], dom[ps, qs] = o, bf16_store(o, Pe), S.argmax(-1)
+    return out, bound, dom

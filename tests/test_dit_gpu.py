@@ -357,14 +357,27 @@ def test_attention_for_head_dims_other_than_64(gpu_device, B, H, Lq, Lk, d):
     vt = ops.v_transposed_hd(kv.view(B, Lk, 2 * H * d)[..., H * d:].unflatten(-1, (H, d)))
     k_n = kv.view(B, Lk, 2 * H * d)[..., :H * d].unflatten(-1, (H, d))
     k_raw = kv_raw.view(B, Lk, 2 * H * d)[..., :H * d].unflatten(-1, (H, d))
+    # beside the norms: every configuration element-wise against float64 with the error model of tests/_bounds.py (two key groups: the
+    # bound of the configuration with the most roundings), from the exact values each launch reads
+    from tests import _attention_cases as ac
+    q_in = q_raw.view(B, Lq, 3 * H * d)[..., :H * d].unflatten(-1, (H, d))
+    z64 = dict(q=q_in.double(), v=v_ref.double(), wq=wq.double(), wk=wk.double())
+    exact = {"q": ac.reference(ac.A("hd_dims_qnorm_inside", "hdv", B, H, Lq, Lk, "flat", d=d, norm="q"), dict(z64, k=k_n.double()), groups=2),
+             "qk": ac.reference(ac.A("hd_dims_qknorm_inside", "hdv", B, H, Lq, Lk, "flat", d=d, norm="qk"), dict(z64, k=k_raw.double()), groups=2)}
+    default_cfg = ops.attention_hd_plan(ac.make_args(ac.A("x", "hdv", B, H, Lq, Lk, "flat", d=d))).config
+    instance = {(p.hd16, p.config): p for p in ops.attention_hd_instances() if p.family == ops.ATTN_HD_FAMILY_HDV}
     for force in ("1", "2", "3", "4", None):      # 4 waves x 16 / x 32 queries, 8 waves x 16, two key groups of 4 x 16, then the launcher's own choice
-        got = _run_hdv(gpu_device, q_raw.view(B, Lq, 3 * H * d)[..., :H * d].unflatten(-1, (H, d)), k_n, vt, wq, None, force)
+        inst = instance[((d + 15) // 16, int(force) if force else default_cfg)]
+        got = _run_hdv(gpu_device, q_in, k_n, vt, wq, None, force)
         assert rel_l2(got.float(), ref) < 1.2e-2, (force, rel_l2(got.float(), ref))
         assert rel_l2(got.float(), out.float()) < 8e-3, (force, rel_l2(got.float(), out.float()))
+        worst = ac.assert_within_bound(f"head dim {d}, configuration {force or 'by shape'}, q norm inside", got, *exact["q"], inst, H, d)
         # ... and k's norm inside as well (every workgroup normalises the key rows it stages)
-        gotk = _run_hdv(gpu_device, q_raw.view(B, Lq, 3 * H * d)[..., :H * d].unflatten(-1, (H, d)), k_raw, vt, wq, wk, force)
+        gotk = _run_hdv(gpu_device, q_in, k_raw, vt, wq, wk, force)
         assert rel_l2(gotk.float(), ref) < 1.2e-2, (force, rel_l2(gotk.float(), ref))
         assert rel_l2(gotk.float(), got.float()) < 4e-3, (force, rel_l2(gotk.float(), got.float()))
+        worstk = ac.assert_within_bound(f"head dim {d}, configuration {force or 'by shape'}, q and k norm inside", gotk, *exact["qk"], inst, H, d)
+        print(f"ATTNCASE hd_dims_d{d}_{Lq}x{Lk}_forced{force or '-'} {ac.describe(inst)} | out {worst:.3f} out(k norm inside) {worstk:.3f}")
     got2 = ops.attention_hd(qkv.view(B, Lq, 3 * H * d)[..., :H * d].unflatten(-1, (H, d)), k_n, vt=vt)     # q and k normalised by the caller
     assert rel_l2(got2.float(), ref) < 1.2e-2
 
