@@ -1,4 +1,4 @@
-"""The cascaded image-to-3D sampling loop around the hot path: what ``FlowMatchingEngine.sample`` and the two sampling
+"""The cascaded image-to-3D / text-to-3D sampling loop around the hot path: what ``FlowMatchingEngine.sample`` and the two sampling
 scripts do between the conditioner and the renderer (/root/reference/nsr/lsgm/flow_matching_trainer.py:700-744 ``sample``;
 :1206-1225 stage hand-off; :1400-1424 ``render_gs_video_given_latent``; shell_scripts/release/inference/i23d/*.sh).
 
@@ -70,6 +70,33 @@ def condition_on_image(embedder, image):
     return cond, {k: torch.zeros_like(v) for k, v in cond.items()}
 
 
+T23D_CFG_SCALE = 4.5  # the guidance scale of both text stages (shell_scripts/release/inference/t23d/stage{1,2}-t23d.sh)
+
+
+@torch.no_grad()
+def condition_on_caption(crossattn, vector):
+    """The conditioning dicts of the t23d release from the two outputs of its caption embedder (``FrozenOpenCLIPEmbedder2``:
+    the token states behind the text tower's last block, ``z["last"]`` [S,77,768], and the pooled, projected vector [S,768] -- computed by the caller, the CLIP text
+    encoder is not part of this package): cond = {'caption_crossattn', 'caption_vector'}; the unconditional half of CFG is all
+    zeros, as ``sgm`` builds it (``GeneralConditioner.forward`` with ``force_zero_embeddings``)."""
+    if crossattn.dim() != 3 or vector.dim() != 2 or crossattn.shape[0] != vector.shape[0]:
+        raise ValueError("caption_crossattn is [S, tokens, width] and caption_vector [S, width]")
+    cond = {"caption_crossattn": crossattn.contiguous(), "caption_vector": vector.contiguous()}
+    return cond, {k: torch.zeros_like(v) for k, v in cond.items()}
+
+
+@torch.no_grad()
+def stage2_caption_conditioning(cond, uc, fps_xyz):
+    """Stage-2 conditioning dicts of the text cascade (stage2-t23d.sh: ``cond_key = caption``): the unconditional caption stays the
+    zero one -- classifier-free guidance is REAL in the text stage 2, unlike the image one -- and both halves share the stage-1 cloud,
+    which the denoiser's XYZPosEmbed sees as ``xyz / 0.45`` (``PCD_Scaler``, as in ``stage2_conditioning``)."""
+    return stage2_conditioning(cond, uc, fps_xyz, zero_image_uc=True)
+
+
+def _is_caption(cond):
+    return "caption_crossattn" in cond
+
+
 @torch.no_grad()
 def stage2_conditioning(cond, uc, fps_xyz, zero_image_uc=False):
     """Stage-2 conditioning dicts from the stage-1 cloud, as the release's conditioner builds them
@@ -90,14 +117,19 @@ def stage2_conditioning(cond, uc, fps_xyz, zero_image_uc=False):
 def cascade(stage1, stage2, decoder, cond, uc, cameras=None, cfg_scale=4.0, seed=42, num_steps=250,
             sampling_method="dopri5", render_all_scale=True, stage2_zero_image_uc=False, stats=None, **ode_kwargs):
     """Stage 1 -> stage 2 -> surfel decode (-> renders when ``cameras`` = {cam_view, cam_view_proj [B,V,4,4], cam_pos
-    [B,V,3], tanfov} is given).  ``cond`` / ``uc``: {'img_crossattn' [S,1369,1024], 'img_vector' [S,1024]}."""
-    S = cond["img_crossattn"].shape[0]
+    [B,V,3], tanfov} is given).  ``cond`` / ``uc``: {'img_crossattn' [S,1369,1024], 'img_vector' [S,1024]} (``condition_on_image``)
+    or, with the text denoisers, {'caption_crossattn' [S,77,768], 'caption_vector' [S,768]} (``condition_on_caption``; the release
+    runs both text stages at ``cfg_scale = T23D_CFG_SCALE``, and its stage 2 is guided against the zero caption)."""
+    S = cond["caption_crossattn" if _is_caption(cond) else "img_crossattn"].shape[0]
     L = decoder.vit_decoder.pos_embed.shape[1]  # 768 latent tokens in the release (z_shape, flow_matching_trainer.py:1158)
     st1, st2 = ({}, {}) if stats is not None else (None, None)
     xyz = sample(stage1, cond, uc, (L, stage1.in_channels), S, cfg_scale, seed, num_steps, sampling_method, stats=st1,
                  **ode_kwargs)
     fps_xyz = (xyz * XYZ_STD).clip(-0.45, 0.45)
-    cond2, uc2 = stage2_conditioning(cond, uc, fps_xyz, zero_image_uc=stage2_zero_image_uc)
+    if _is_caption(cond):
+        cond2, uc2 = stage2_caption_conditioning(cond, uc, fps_xyz)
+    else:
+        cond2, uc2 = stage2_conditioning(cond, uc, fps_xyz, zero_image_uc=stage2_zero_image_uc)
     latent = sample(stage2, cond2, uc2, (L, stage2.in_channels), S, cfg_scale, seed, num_steps, sampling_method,
                     stats=st2, **ode_kwargs)
     if stats is not None:

@@ -168,6 +168,9 @@ int attention_with_tail(const GaAttentionArgs *a, const ShiftBiasJob *job, void 
 int attention_workgroups(const GaAttentionArgs *a);
 bool attention_fuses_q(const GaAttentionArgs *a);
 int attention_tail_check(const ShiftBiasJob *job, const PrefetchJob *pf);   // the validation of a tail's jobs (both attention files)
+// dit_attention_short.hip: the short-context kernel (Lk <= 128) with prefetch tail workgroups behind its grid
+int attention_short_with_tail(const GaAttentionArgs *a, void *stream, const PrefetchJob *pf, int pf_wgs);
+int attention_short_workgroups(const GaAttentionArgs *a);
 // dit_attention_hd.hip: the V^T variant for head dims other than 64 with prefetch tail workgroups behind its grid
 int attention_hd_with_tail(const GaAttentionHdArgs *a, void *stream, const PrefetchJob *pf, int pf_wgs, const ShiftBiasJob *job = nullptr);
 int attention_hd_workgroups(const GaAttentionHdArgs *a);

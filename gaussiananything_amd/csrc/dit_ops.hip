@@ -319,6 +319,8 @@ struct FinalArgs {
     float *state, *traj;
     long long traj_stride;
     const int *counter;
+    // FinalLayer of the text models (GaDitModel.final_adaln_w): rows [b][shift D | scale D] = Linear(SiLU(t)) in place of table + t
+    const float *fmod;
 };
 
 // One wave per row, the row (D <= 2048, D % 4 == 0) held in registers as in rmsnorm_modulate_kernel: one memory round trip
@@ -349,6 +351,11 @@ __device__ __forceinline__ void final_layer_row(const FinalArgs &a, int row, int
         const int d = c * 256 + lane * 4;
         if (d < D) {
             v[c] = *reinterpret_cast<const float4 *>(x + d);
+            if (a.fmod) {      // kernel-uniform
+                sh[c] = *reinterpret_cast<const float4 *>(a.fmod + (size_t)b * 2 * D + d);
+                sc[c] = *reinterpret_cast<const float4 *>(a.fmod + (size_t)b * 2 * D + D + d);
+                continue;
+            }
             const float4 t4 = *reinterpret_cast<const float4 *>(tb + d);
             const float4 h4 = *reinterpret_cast<const float4 *>(a.table + d);
             const float4 s4 = *reinterpret_cast<const float4 *>(a.table + D + d);
@@ -478,6 +485,20 @@ __global__ __launch_bounds__(256) void final_layer_kernel(FinalArgs a, int w_in_
     }
 }
 
+// out[r][:] = bf16(rmsnorm(x[r][:]; eps) * w[:]) on bf16 rows: attention_y_norm of the text blocks on the caption tokens, once per
+// conditioning (ga_dit_cache_context_ws).  One wave per row, any D.
+__global__ __launch_bounds__(256) void ctx_rmsnorm_kernel(const uint16_t *__restrict__ x, const float *__restrict__ w, uint16_t *__restrict__ out,
+                                                          int rows, int D, float eps)
+{
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const uint16_t *xr = x + (size_t)row * D;
+    float ss = 0.f;
+    for (int d = lane; d < D; d += 64) { const float v = bf16_to_f32(xr[d]); ss += v * v; }
+    const float rs = rsqrtf(wave_sum(ss) / (float)D + eps);
+    for (int d = lane; d < D; d += 64) out[(size_t)row * D + d] = f32_to_bf16(bf16_to_f32(xr[d]) * rs * w[d]);
+}
+
 __global__ void sampler_advance_kernel(int *counter, const float *t_grid, const float *dt_grid, int grid_len, float *timesteps,
                                        int batch, float *dt)
 {
@@ -529,7 +550,7 @@ extern "C" int ga_dit_shift_bias(const ga_bf16 *W, int32_t w_tiled, const float 
 namespace gadit {
 
 struct Ws {
-    float *xres, *tfreq, *t1, *pln, *pvec, *tvec, *t0, *mod, *rowss, *sbias;
+    float *xres, *tfreq, *t1, *pln, *pvec, *tvec, *t0, *mod, *rowss, *sbias, *fmod;
     uint16_t *xn, *qkv, *att, *hmid, *vt;
     size_t vt_bytes;
     void *splitk;          // scratch of the deterministic split-K of fc2 (GaGemmArgs.splitk_ws); nullptr above 3072 rows
@@ -564,6 +585,9 @@ static Ws carve(const GaDitModel *m, int B, int L, void *base)
                                           GA_GEMM_SPLITK_COUNTER_BYTES + (ga_gemm_splitk_workspace_bytes((int32_t)M, (int32_t)(4 * D)) - GA_GEMM_SPLITK_COUNTER_BYTES) / 2) : 0;
     const size_t o_sk = take(w.splitk_bytes);
     w.splitk = w.splitk_bytes && base ? p + o_sk : nullptr;
+    // (shift | scale) rows of the text models' FinalLayer; the image models' workspace is what it was
+    const size_t o_fmod = m->final_adaln_w ? take((size_t)B * 2 * D * 4) : 0;
+    w.fmod = m->final_adaln_w ? reinterpret_cast<float *>(p + o_fmod) : nullptr;
     w.total = off;
     w.xres = reinterpret_cast<float *>(p + o_xres); w.xn = reinterpret_cast<uint16_t *>(p + o_xn);
     w.qkv = reinterpret_cast<uint16_t *>(p + o_qkv); w.att = reinterpret_cast<uint16_t *>(p + o_att);
@@ -585,6 +609,16 @@ static bool can_fold(const GaDitModel *m, int i)
     const bool w256 = D % 256 == 0 && D <= 1024;
     const bool width_ok = m->hidden / m->heads == 64 ? w256 : (w256 || (D % 192 == 0 && D <= 1280));
     return m->blocks[i].ca_q_w_prenorm != nullptr && width_ok;
+}
+
+// the text-model fields (block order, FinalLayer): checked by ga_dit_forward and ga_dit_cache_context_ws before anything is enqueued
+static int text_fields_rc(const GaDitModel *m)
+{
+    if (m->block_order != 0 && m->block_order != 1) return GA_DIT_ERR_BAD_SHAPE;
+    if (m->block_order == 1 && m->hidden / m->heads != 64) return GA_DIT_ERR_BAD_SHAPE;   // (include/ga_dit.h: refused, not built)
+    if ((m->final_adaln_w == nullptr) != (m->final_adaln_b == nullptr)) return GA_DIT_ERR_NULL_ARG;
+    if (!m->final_adaln_w && !m->final_table) return GA_DIT_ERR_NULL_ARG;
+    return GA_DIT_OK;
 }
 
 static bool model_ok(const GaDitModel *m)
@@ -615,18 +649,43 @@ static int ga_skip_mask() { static const int v = [] { const char *e = getenv("GA
 #define GA_UNLESS(bit, expr) GA_TRY(expr)
 #endif
 
+extern "C" size_t ga_dit_context_scratch_bytes(const GaDitModel *m, int32_t batch, int32_t ctx_tokens)
+{
+    if (!gadit::model_ok(m) || batch <= 0 || ctx_tokens <= 0) return 0;
+    for (int i = 0; i < m->depth; ++i)
+        if (m->blocks[i].ctx_norm_w) return gadit::al256((size_t)batch * ctx_tokens * m->context_dim * sizeof(ga_bf16));
+    return 0;
+}
+
 extern "C" int ga_dit_cache_context(const GaDitModel *m, int32_t batch, int32_t ctx_tokens, const ga_bf16 *ctx,
                                     ga_bf16 *ca_k, ga_bf16 *ca_vt, void *stream)
 {
+    return ga_dit_cache_context_ws(m, batch, ctx_tokens, ctx, ca_k, ca_vt, nullptr, 0, stream);
+}
+
+extern "C" int ga_dit_cache_context_ws(const GaDitModel *m, int32_t batch, int32_t ctx_tokens, const ga_bf16 *ctx,
+                                       ga_bf16 *ca_k, ga_bf16 *ca_vt, void *scratch, size_t scratch_bytes, void *stream)
+{
     if (!gadit::model_ok(m) || !ctx || !ca_k || !ca_vt) return GA_DIT_ERR_NULL_ARG;
     if (batch <= 0 || ctx_tokens <= 0) return GA_DIT_ERR_BAD_SHAPE;
+    GA_TRY(gadit::text_fields_rc(m));
+    const size_t need = ga_dit_context_scratch_bytes(m, batch, ctx_tokens);
+    if (need && !scratch) return GA_DIT_ERR_NULL_ARG;
+    if (need && (scratch_bytes < need || ((uintptr_t)scratch & 255))) return GA_DIT_ERR_BAD_SHAPE;
     const int rows = batch * ctx_tokens, D = m->hidden;
     const int64_t Mp = ((int64_t)ctx_tokens + 63) / 64 * 64;
     const bool hd64 = D / m->heads == 64;   // other head dims (ga_attention_hd_bf16): the same K | V^T images, k's per-head norm as a pass of its own
     for (int i = 0; i < m->depth; ++i) {
         GaGemmArgs g{};
         g.M = rows; g.N = 2 * D; g.K = m->context_dim; g.epilogue = GA_GEMM_EPI_STORE_BF16;
-        g.A = ctx; g.lda = m->context_dim; g.W = m->blocks[i].ca_kv_w; g.w_tiled = m->gemm_weights_tiled; g.bias = nullptr;
+        g.A = ctx;
+        if (m->blocks[i].ctx_norm_w) {   // this block's attention_y_norm of the tokens, then the same projection (launches of one stream: the scratch is reused)
+            hipLaunchKernelGGL(gadit::ctx_rmsnorm_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), ctx,
+                               m->blocks[i].ctx_norm_w, static_cast<uint16_t *>(scratch), rows, m->context_dim, 1e-5f);
+            if (hipGetLastError() != hipSuccess) return GA_DIT_ERR_LAUNCH;
+            g.A = static_cast<const ga_bf16 *>(scratch);
+        }
+        g.lda = m->context_dim; g.W = m->blocks[i].ca_kv_w; g.w_tiled = m->gemm_weights_tiled; g.bias = nullptr;
         g.out = ca_k + (size_t)i * rows * D; g.ldo = D;                    // K columns [0, D)
         g.vt = ca_vt + (size_t)i * batch * D * Mp; g.vt_col0 = D; g.vt_ld = Mp; g.rows_per_batch = ctx_tokens;
         if (hd64) { g.qk_w0 = m->blocks[i].ca_k_norm_w; g.qk_cols0 = D; g.qk_cols1 = D; }  // k_norm applied once, here
@@ -682,6 +741,8 @@ extern "C" int ga_dit_forward(const GaDitModel *m, const GaDitForwardArgs *a, vo
     // a sampler step writes states / velocities of in_channels floats per token: a model that also predicts sigma (out_channels !=
     // in_channels) has no such step -- refused before anything is enqueued (the reference trips body_fn's shape assert there)
     if (a->step && (m->out_channels != m->in_channels || (a->step->cfg && (B % 2 != 0)))) return GA_DIT_ERR_BAD_SHAPE;
+    GA_TRY(text_fields_rc(m));
+    const bool order1 = m->block_order == 1;     // self-attention, cross-attention, MLP: the text models (see the block loop)
     const Ws w = carve(m, B, L, a->workspace);
     if (a->workspace_bytes < w.total || ((uintptr_t)a->workspace & 255)) return GA_DIT_ERR_BAD_SHAPE;
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -697,7 +758,7 @@ extern "C" int ga_dit_forward(const GaDitModel *m, const GaDitForwardArgs *a, vo
     // dopri5 evaluation, 3.06 -> 3.16 eager -- a cross-stream dependency costs this runtime ~45 us per hop, more than the ~25 us of
     // chain it hides (the same sign as round 4's two concurrent CFG halves)
     static const bool fork_env = [] { const char *e = getenv("GA_DIT_FORK"); return e && atoi(e) != 0; }();
-    SideStream *fk = fork_env ? &side_stream() : nullptr;
+    SideStream *fk = fork_env && !order1 ? &side_stream() : nullptr;   // (order 1: the token embedding's GEMM already consumes the chain's results)
     if (fk && (!fk->ok || hipEventRecord(fk->fork, s) != hipSuccess || hipStreamWaitEvent(fk->side, fk->fork, 0) != hipSuccess)) fk = nullptr;
     hipStream_t cs = fk ? fk->side : s;      // the conditioning chain's stream
     void *cstream = reinterpret_cast<void *>(cs);
@@ -729,7 +790,9 @@ extern "C" int ga_dit_forward(const GaDitModel *m, const GaDitForwardArgs *a, vo
     //  bandwidth-sized and the fold is 1 % behind -- left off there)
     static const bool fold_mod_env = [] { const char *e = getenv("GA_DIT_FOLD_MOD"); return !e || atoi(e) != 0; }();   // A/B aid
     static const int fold_rows = [] { const char *e = getenv("GA_DIT_FOLD_ROWS"); return e ? atoi(e) : 3072; }();                      // A/B aid
-    const bool fold_mod = fold_mod_env && can_fold(m, 0) && m->depth <= 64 && Mrows <= fold_rows;
+    bool fold_all = true;                        // order 1 folds all three pre-norms of every block or none
+    for (int i = 0; order1 && i < m->depth; ++i) fold_all = fold_all && can_fold(m, i);
+    const bool fold_mod = fold_mod_env && can_fold(m, 0) && fold_all && m->depth <= 64 && Mrows <= fold_rows;
     static const bool sb_tail_env = [] { const char *e = getenv("GA_DIT_SBTAIL"); return !e || atoi(e) != 0; }();
     // the shift rows of block i + 1 ride behind the self-attention grid of block i while that grid leaves CUs idle (a CFG pair: 192
     // workgroups + 56 of the tail on 256 CUs); on a full grid they would queue behind it (8 items: 9.2 -> 9.8 ms) -- one launch up front then
@@ -751,7 +814,7 @@ extern "C" int ga_dit_forward(const GaDitModel *m, const GaDitForwardArgs *a, vo
         // the stand-alone 12 us launch in front of the blocks is gone when that grid leaves the CUs free as well
         const GaAttentionArgs probe_ca{ca_batch, m->heads, L, a->ctx_tokens, nullptr, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, nullptr, 0};
         static const bool sb_tail0_env = [] { const char *e = getenv("GA_DIT_SBTAIL0"); return !e || atoi(e) != 0; }();   // A/B aid
-        sb_tail0 = sb_tail0_env && sb_tail && attention_workgroups(&probe_ca) + shift_bias_wgs(3 * D, 4 * D) <= ncu;
+        sb_tail0 = !order1 && sb_tail0_env && sb_tail && attention_workgroups(&probe_ca) + shift_bias_wgs(3 * D, 4 * D) <= ncu;
     }
     // Round 6: WEIGHT PREFETCH.  A GEMM whose weights sit in the Infinity Cache instead of HBM starts and streams faster (fc2 at 1536
     // rows 24.0 -> 21.1 us, at 768 rows 19.3 -> 15.7; fc1 18.0 -> 17.1; tools/warm_vs_cold.py), and every attention grid of a CFG pair
@@ -794,6 +857,10 @@ extern "C" int ga_dit_forward(const GaDitModel *m, const GaDitForwardArgs *a, vo
         GaGemmArgs g{};
         g.M = Mrows; g.N = D; g.K = D; g.epilogue = GA_GEMM_EPI_RESIDUAL; g.A = w.xn; g.lda = D; g.W = m->xe_fc2_w; g.w_tiled = m->gemm_weights_tiled;
         g.bias = m->xe_fc2_b; g.out = w.xres; g.ldo = D; g.gate = nullptr; g.rows_per_batch = L;
+        if (order1 && fold_mod) {   // block 0 starts with its self-attention: the modulated norm1 operand leaves through this epilogue
+            g.emit_x = w.xn; g.emit_ld = D; g.emit_ss = w.rowss; g.emit_w = m->blocks[0].norm1_w; g.emit_scale = w.mod + 1 * D;
+            g.emit_scale_stride = 6 * (int64_t)D;
+        }
         GA_TRY(ga_gemm_bf16(&g, stream));
     }
     const size_t kv_rows = (size_t)B * a->ctx_tokens;
@@ -807,6 +874,126 @@ extern "C" int ga_dit_forward(const GaDitModel *m, const GaDitForwardArgs *a, vo
         // into the neighbouring GEMMs: the previous block's fc2 epilogue left bf16(x) in xn and the rows' sums of squares in
         // rowss (below); the q projection, with the norm weight folded into its columns, applies rsqrt(mean + eps) to its rows.
         const bool folded = i > 0 && can_fold(m, i);
+        if (order1) {
+            // SELF-ATTENTION, CROSS-ATTENTION, MLP (PixelArtTextCondDiTBlock, dit_models_xformers.py:357-376), heads of 64.  The same eleven launches
+            // as order 0 with the three pre-norm folds re-wired (fold_mod; otherwise three norm launches):
+            //   fc2 of the block before (block 0: the token embedding's GEMM) emits the MODULATED norm1 operand     -> qkv, with its shift rows
+            //   proj emits the UN-modulated prenorm_ca_text operand                                                -> the q projection (ca_q_w_prenorm)
+            //   the cross-attention output GEMM, over all rows with k_rows, emits the MODULATED norm2 operand      -> fc1, with its shift rows
+            // Tails: block 0's shift rows are the launch up front (its qkv is the block's first GEMM); block i + 1's ride behind block i's
+            // SELF-attention grid (the round-4 placement of order 0: their first consumer, qkv, is the next block's first GEMM); the weight
+            // prefetch rides behind the CROSS-attention grid, on the CUs it leaves idle (GA_DIT_T_PREFETCH=0: off, A/B aid;
+            // profiles/t23d_short_ca_ab.txt)
+            static const bool t_pf = [] { const char *e = getenv("GA_DIT_T_PREFETCH"); return !e || atoi(e) != 0; }();
+            const float *sbias = w.sbias + (size_t)i * B * 7 * D;   // [B][3D] qkv | [B][4D] fc1
+            if (!fold_mod) {
+                GaRmsNormArgs n1{Mrows, D, L, w.xres, bw.norm1_w, mod + 1 * D, mod + 0 * D, 6 * (int64_t)D, w.xn, nullptr, 0};
+                GA_TRY(ga_rmsnorm_modulate(&n1, stream));
+            }
+            GaGemmArgs gqkv{};
+            gqkv.M = Mrows; gqkv.N = 3 * D; gqkv.K = D; gqkv.epilogue = GA_GEMM_EPI_STORE_BF16; gqkv.A = w.xn; gqkv.lda = D;
+            gqkv.W = bw.qkv_w; gqkv.w_tiled = m->gemm_weights_tiled; gqkv.bias = bw.qkv_b; gqkv.out = w.qkv; gqkv.ldo = 2 * D;   // q | k row-major ...
+            gqkv.vt = w.vt; gqkv.vt_col0 = 2 * D; gqkv.vt_ld = Lp; gqkv.rows_per_batch = L;  // ... v transposed
+            gqkv.qk_w0 = bw.q_norm_w; gqkv.qk_cols0 = D; gqkv.qk_w1 = bw.k_norm_w; gqkv.qk_cols1 = 2 * D;  // per-head q/k RMSNorm
+            if (fold_mod) {
+                gqkv.row_ss = w.rowss; gqkv.row_ss_tiles = D / 64; gqkv.row_ss_dim = D; gqkv.row_ss_eps = 1e-5f;
+                gqkv.bias = sbias; gqkv.bias_stride = 3 * (int64_t)D;
+            }
+            gqkv.splitk_ws = w.splitk; gqkv.splitk_ws_bytes = (int64_t)w.splitk_bytes;
+            GA_TRY(ga_gemm_bf16(&gqkv, stream));
+            GaAttentionArgs sa{B, m->heads, L, L, w.qkv, w.qkv + D, w.vt, 2 * D, 2 * D, Lp, nullptr, nullptr, w.att, D};
+            if (fold_mod && sb_tail && i + 1 < m->depth) {
+                const GaDitBlockWeights &nb = m->blocks[i + 1];
+                ShiftBiasJob job{{nb.qkv_w, nb.fc1_w}, {nb.qkv_b, nb.fc1_b}, w.mod + (size_t)(i + 1) * B * 6 * D, w.sbias + (size_t)(i + 1) * B * 7 * D,
+                                 6 * (long long)D, 3 * (long long)D, 3 * D, 4 * D, D, B, m->gemm_weights_tiled};
+                GA_TRY(attention_with_tail(&sa, &job, stream, nullptr, 0));
+            } else
+                GA_TRY(ga_attention_bf16(&sa, stream));
+            GaGemmArgs gp{};
+            gp.M = Mrows; gp.N = D; gp.K = D; gp.epilogue = GA_GEMM_EPI_RESIDUAL; gp.A = w.att; gp.lda = D; gp.W = bw.proj_w; gp.w_tiled = m->gemm_weights_tiled;
+            gp.bias = bw.proj_b; gp.out = w.xres; gp.ldo = D; gp.gate = mod + 2 * D; gp.gate_stride = 6 * (int64_t)D; gp.rows_per_batch = L;
+            if (fold_mod) { gp.emit_x = w.xn; gp.emit_ld = D; gp.emit_ss = w.rowss; }      // bf16(x) and the rows' sums of squares: prenorm_ca_text
+            GA_TRY(ga_gemm_bf16(&gp, stream));
+            if (!fold_mod) {
+                GaRmsNormArgs n0{Mca, D, L, w.xres, bw.prenorm_ca_w, nullptr, nullptr, 0, w.xn, nullptr, 0};
+                GA_TRY(ga_rmsnorm_modulate(&n0, stream));
+            }
+            GaAttentionArgs ca{ca_batch, m->heads, L, a->ctx_tokens, w.qkv, a->ca_k + (size_t)i * kv_rows * D,
+                               a->ca_vt + (size_t)i * B * D * Mp, D, D, Mp, nullptr, nullptr, w.att, D};
+            static const bool fuse_q_env1 = [] { const char *e = getenv("GA_DIT_FUSE_Q"); return !e || atoi(e) != 0; }();
+            // the short-context kernel (ga_attention_short_bf16, q projected inside) for key lists that fit LDS whole.  GA_DIT_SHORT_CA: 0 the
+            // long-list kernel | 1 (default) the short one, except where its 64-query grid leaves the prefetch tail no CUs while the long-list
+            // kernel's grid does (CFG batch 4: 384 against 192 workgroups) | 2 the short one always.  Measured: profiles/t23d_short_ca_ab.txt
+            static const int short_env = [] { const char *e = getenv("GA_DIT_SHORT_CA"); return e ? atoi(e) : 1; }();
+            bool short_ca = a->ctx_tokens <= 128 && short_env > 0;
+            if (short_env == 1 && short_ca && t_pf && pf_ca >= 16 && ncu - attention_short_workgroups(&ca) < 16) short_ca = false;
+            if (short_ca || (fuse_q_env1 && attention_fuses_q(&ca))) {
+                ca.q = nullptr;
+                ca.qp_a = w.xn; ca.qp_lda = D; ca.qp_k = D; ca.qp_w = fold_mod ? bw.ca_q_w_prenorm : bw.ca_q_w; ca.qp_w_tiled = m->gemm_weights_tiled;
+                if (fold_mod) { ca.qp_row_ss = w.rowss; ca.qp_row_ss_tiles = D / 64; ca.qp_row_ss_dim = D; ca.qp_row_ss_eps = 1e-5f; }
+                ca.q_norm_weight = bw.ca_q_norm_w;
+            } else {
+                GaGemmArgs gq{};
+                gq.M = Mca; gq.N = D; gq.K = D; gq.epilogue = GA_GEMM_EPI_STORE_BF16; gq.A = w.xn; gq.lda = D;
+                gq.W = fold_mod ? bw.ca_q_w_prenorm : bw.ca_q_w; gq.w_tiled = m->gemm_weights_tiled;
+                gq.out = w.qkv; gq.ldo = D;
+                if (fold_mod) { gq.row_ss = w.rowss; gq.row_ss_tiles = D / 64; gq.row_ss_dim = D; gq.row_ss_eps = 1e-5f; }
+                gq.qk_w0 = bw.ca_q_norm_w; gq.qk_cols0 = D; gq.qk_cols1 = D;           // q_norm fused into the projection
+                GA_TRY(ga_gemm_bf16(&gq, stream));
+            }
+            // weight prefetch by the tail workgroups behind this grid (what it leaves of the CUs, as on the other grids): this block's fc2,
+            // the next block's self-attention output and cross-attention q / out weights (after the last block: block 0 of the next evaluation)
+            PrefetchJob pf{};
+            int pf_ca1 = 0;
+            if (t_pf && pf_mode > 0) {
+                const unsigned DD = (unsigned)D * (unsigned)D;
+                const GaDitBlockWeights &nb = m->blocks[i + 1 < m->depth ? i + 1 : 0];
+                pf.ptr[0] = reinterpret_cast<const char *>(bw.fc2_w); pf.bytes[0] = 8u * DD;
+                pf.ptr[1] = reinterpret_cast<const char *>(nb.ca_out_w); pf.bytes[1] = 2u * DD;
+                pf.ptr[2] = reinterpret_cast<const char *>(fold_mod ? nb.ca_q_w_prenorm : nb.ca_q_w); pf.bytes[2] = 2u * DD;
+                pf.ptr[3] = reinterpret_cast<const char *>(nb.proj_w); pf.bytes[3] = 2u * DD;
+                pf_ca1 = short_ca ? std::min(64, std::max(0, ncu - attention_short_workgroups(&ca))) : pf_ca;
+                if (pf_ca1 < 16) pf_ca1 = 0;
+            }
+            if (short_ca)
+                GA_TRY(attention_short_with_tail(&ca, stream, pf_ca1 ? &pf : nullptr, pf_ca1));
+            else if (pf_ca1)
+                GA_TRY(attention_with_tail(&ca, nullptr, stream, &pf, pf_ca1));
+            else
+                GA_TRY(ga_attention_bf16(&ca, stream));
+            GaGemmArgs go{};
+            go.M = Mca; go.N = D; go.K = D; go.epilogue = GA_GEMM_EPI_RESIDUAL; go.A = w.att; go.lda = D; go.W = bw.ca_out_w; go.w_tiled = m->gemm_weights_tiled;
+            go.bias = bw.ca_out_b; go.out = w.xres; go.ldo = D; go.gate = nullptr; go.rows_per_batch = L;
+            if (fold_mod) {     // over ALL rows (the items that skipped the cross-attention take the bias with a zero product), emitting norm2's operand
+                go.M = Mrows; go.k_rows = Mca;
+                go.emit_x = w.xn; go.emit_ld = D; go.emit_ss = w.rowss; go.emit_w = bw.norm2_w; go.emit_scale = mod + 4 * D; go.emit_scale_stride = 6 * (int64_t)D;
+            }
+            GA_TRY(ga_gemm_bf16(&go, stream));
+            if (!fold_mod) {    // (rows of the items that skipped the cross-attention pick up its output bias here)
+                GaRmsNormArgs n2{Mrows, D, L, w.xres, bw.norm2_w, mod + 4 * D, mod + 3 * D, 6 * (int64_t)D, w.xn, Mca < Mrows ? bw.ca_out_b : nullptr, Mca};
+                GA_TRY(ga_rmsnorm_modulate(&n2, stream));
+            }
+            GaGemmArgs g1{};
+            g1.M = Mrows; g1.N = 4 * D; g1.K = D; g1.epilogue = GA_GEMM_EPI_GELU_BF16; g1.A = w.xn; g1.lda = D; g1.W = bw.fc1_w; g1.w_tiled = m->gemm_weights_tiled;
+            g1.bias = bw.fc1_b; g1.out = w.hmid; g1.ldo = 4 * D;
+            if (fold_mod) {
+                g1.row_ss = w.rowss; g1.row_ss_tiles = D / 64; g1.row_ss_dim = D; g1.row_ss_eps = 1e-5f;
+                g1.bias = sbias + (size_t)B * 3 * D; g1.bias_stride = 4 * (int64_t)D; g1.rows_per_batch = L;
+            }
+            g1.splitk_ws = w.splitk; g1.splitk_ws_bytes = (int64_t)w.splitk_bytes;
+            GA_TRY(ga_gemm_bf16(&g1, stream));
+            GaGemmArgs g2{};
+            g2.M = Mrows; g2.N = D; g2.K = 4 * D; g2.epilogue = GA_GEMM_EPI_RESIDUAL; g2.A = w.hmid; g2.lda = 4 * D;
+            g2.W = bw.fc2_w; g2.w_tiled = m->gemm_weights_tiled; g2.bias = bw.fc2_b; g2.out = w.xres; g2.ldo = D; g2.gate = mod + 5 * D;
+            g2.gate_stride = 6 * (int64_t)D; g2.rows_per_batch = L;
+            if (fold_mod && i + 1 < m->depth) {   // the next block's modulated norm1 operand
+                g2.emit_x = w.xn; g2.emit_ld = D; g2.emit_ss = w.rowss; g2.emit_w = m->blocks[i + 1].norm1_w;
+                g2.emit_scale = w.mod + (size_t)(i + 1) * B * 6 * D + 1 * D; g2.emit_scale_stride = 6 * (int64_t)D;
+            }
+            g2.splitk_ws = w.splitk; g2.splitk_ws_bytes = (int64_t)w.splitk_bytes;
+            GA_TRY(ga_gemm_bf16(&g2, stream));
+            continue;
+        }
         if (hd != 64) {
             // HEAD DIMS OTHER THAN 64 (DiT-PixArt-PCD-CLAY-XL: 16 heads of 72): the same block without the attention-launch tails -- k's per-head
             // norm as a pass of its own (the GEMM epilogue's is 64-wide), ga_attention_hd_bf16 on q | k row-major + V^T
@@ -1038,7 +1225,12 @@ extern "C" int ga_dit_forward(const GaDitModel *m, const GaDitForwardArgs *a, vo
     }
     {
         FinalArgs f{Mrows, D, m->out_channels, L, w.xres, m->final_table, w.tvec, m->final_w, m->final_b, a->out,
-                    0.f, 0, nullptr, nullptr, nullptr, 0, nullptr};
+                    0.f, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr};
+        if (m->final_adaln_w) {    // FinalLayer: (shift | scale) = adaLN_modulation(t) = Linear(SiLU(t)), one row per batch item
+            GaSmallLinearArgs lf{B, 2 * D, D, 1, 0, w.tvec, m->final_adaln_w, m->final_adaln_b, nullptr, w.fmod};
+            if (ga_small_linear(&lf, stream) != GA_DIT_OK) return GA_DIT_ERR_LAUNCH;
+            f.fmod = w.fmod;
+        }
         int rows = Mrows;
         if (const GaDitSamplerStep *st = a->step) {
             if (st->velocity) {     // the (guided) velocity alone: dt == nullptr tells the kernel

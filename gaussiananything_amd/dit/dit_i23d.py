@@ -146,6 +146,10 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
         self.pooled_vec_embedder = nn.Sequential(nn.LayerNorm(self.context_dim), nn.Linear(self.context_dim, D))
         self._stage2 = _stage2
         self.initialize_weights()
+        self._init_runtime_state()
+
+    def _init_runtime_state(self):
+        """what the host code below keeps per module besides the parameters (every constructor of the family ends with this)"""
         self._pack = None
         self._ctx_cache = None
         self._busy = threading.RLock()        # see _exclusive()
@@ -227,29 +231,31 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
 
         blocks = (ops.GaDitBlockWeights * self.depth)()
         for i, b in enumerate(self.blocks):
-            ca = b.cross_attn_dino
+            ca, prenorm = getattr(b, self._ca_name), getattr(b, self._ca_prenorm_name)
             blocks[i] = ops.GaDitBlockWeights(
-                fp(b.prenorm_ca_dino.weight), gw(ca.to_q.weight),
-                gw(ca.to_q.weight.detach().float() * b.prenorm_ca_dino.weight.detach().float()[None, :]) if self.fold_prenorm else None,
+                fp(prenorm.weight), gw(ca.to_q.weight),
+                gw(ca.to_q.weight.detach().float() * prenorm.weight.detach().float()[None, :]) if self.fold_prenorm else None,
                 gw(torch.cat([ca.to_k.weight, ca.to_v.weight], 0)),
                 fp(ca.q_norm.weight), fp(ca.k_norm.weight), gw(ca.to_out[0].weight), fp(ca.to_out[0].bias),
                 fp(b.norm1.weight), gw(b.attn.qkv.weight), fp(b.attn.qkv.bias), fp(b.attn.q_norm.weight),
                 fp(b.attn.k_norm.weight), gw(b.attn.proj.weight), fp(b.attn.proj.bias), fp(b.norm2.weight),
                 gw(b.mlp.mlp[0].weight), fp(b.mlp.mlp[1].bias), gw(b.mlp.mlp[2].weight), fp(b.mlp.mlp[3].bias),
-                fp(b.scale_shift_table))
+                fp(b.scale_shift_table), fp(b.attention_y_norm.weight) if self._ctx_norm else None)
         xyz_w = xyz_b = None
         if self._stage2:
             xyz_w, xyz_b = fp(self.xyz_pos_embed.xyz_projection.weight), fp(self.xyz_pos_embed.xyz_projection.bias)
+        pooled = getattr(self, self._pooled_name)               # LayerNorm(affine) + Linear of the pooled conditioning vector
+        final_adaln = self.final_layer.adaLN_modulation[1] if self._block_order == 1 else None   # FinalLayer of the text models
         model = ops.GaDitModel(
             self.embed_dim, self.depth, self.num_heads, self.in_channels, self.out_channels, self.context_dim,
             1 if self._stage2 else 0,
             bf(self.t_embedder.mlp[0].weight), fp(self.t_embedder.mlp[0].bias), bf(self.t_embedder.mlp[2].weight),
-            fp(self.t_embedder.mlp[2].bias), fp(self.pooled_vec_embedder[0].weight), fp(self.pooled_vec_embedder[0].bias),
-            bf(self.pooled_vec_embedder[1].weight), fp(self.pooled_vec_embedder[1].bias),
+            fp(self.t_embedder.mlp[2].bias), fp(pooled[0].weight), fp(pooled[0].bias), bf(pooled[1].weight), fp(pooled[1].bias),
             bf(self.adaLN_modulation[1].weight), fp(self.adaLN_modulation[1].bias), fp(self.x_embedder.fc1.weight),
             fp(self.x_embedder.fc1.bias), gw(self.x_embedder.fc2.weight), fp(self.x_embedder.fc2.bias), xyz_w, xyz_b,
-            fp(self.final_layer.scale_shift_table), fp(self.final_layer.linear.weight), fp(self.final_layer.linear.bias),
-            blocks, 1 if tiled else 0)
+            fp(self.final_layer.scale_shift_table) if final_adaln is None else None,
+            fp(self.final_layer.linear.weight), fp(self.final_layer.linear.bias), blocks, 1 if tiled else 0, self._block_order,
+            bf(final_adaln.weight) if final_adaln is not None else None, fp(final_adaln.bias) if final_adaln is not None else None)
         self._pack = dict(sig=sig, device=device, model=model, blocks=blocks, keep=keep, ws=None, ws_key=None)
         self._ctx_cache = None
         self._pooled_cache = None
@@ -263,6 +269,12 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
         every call, so they never serve a stale projection."""
         self._ctx_cache = None
         self._pooled_cache = None
+
+    # What tells the caption-conditioned twins (dit/dit_trilatent.py) from these models, for the shared host code: the context keys,
+    # the names of the cross-attention modules, the block order / final layer (GaDitModel.block_order) and the per-block context norm
+    _ctx_key, _vec_key = "img_crossattn", "img_vector"
+    _ca_name, _ca_prenorm_name, _pooled_name = "cross_attn_dino", "prenorm_ca_dino", "pooled_vec_embedder"
+    _block_order, _ctx_norm = 0, False
 
     ca_skip = True  # skip the cross-attention of batch items whose image tokens are all zero (exact; tests switch it off)
     # fold the (un-modulated) cross-attention pre-norm into the neighbouring GEMMs (include/ga_dit.h); GA_DIT_FOLD=0: A/B aid
@@ -286,8 +298,15 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
             ck = torch.empty((self.depth, B * M, kcols), dtype=torch.bfloat16, device=ctx.device)
             cvt = torch.zeros((self.depth, B * self.embed_dim, Mp), dtype=torch.bfloat16, device=ctx.device)
         stream = ctypes.c_void_p(torch.cuda.current_stream(ctx.device).cuda_stream)
-        ops.check(ops.lib().ga_dit_cache_context(ctypes.byref(pack["model"]), B, M, ctx.data_ptr(), ck.data_ptr(),
-                                                 cvt.data_ptr(), stream), "ga_dit_cache_context")
+        if self._ctx_norm:     # every block normalises the tokens itself before its to_k / to_v: a scratch for the normalised copy
+            nscr = ops.lib().ga_dit_context_scratch_bytes(ctypes.byref(pack["model"]), B, M)
+            scr = torch.empty(nscr + 256, dtype=torch.uint8, device=ctx.device)
+            ops.check(ops.lib().ga_dit_cache_context_ws(ctypes.byref(pack["model"]), B, M, ctx.data_ptr(), ck.data_ptr(), cvt.data_ptr(),
+                                                        scr.data_ptr() + ((-scr.data_ptr()) % 256), nscr, stream), "ga_dit_cache_context_ws")
+            scr.record_stream(torch.cuda.current_stream(ctx.device))
+        else:
+            ops.check(ops.lib().ga_dit_cache_context(ctypes.byref(pack["model"]), B, M, ctx.data_ptr(), ck.data_ptr(),
+                                                     cvt.data_ptr(), stream), "ga_dit_cache_context")
         # leading batch items with a non-zero context; the all-zero ones (unconditional half of a CFG batch) skip the
         # cross-attention exactly (include/ga_dit.h: ca_batch).  One host read per conditioning tensor.
         nz = (ctx_tokens.detach().reshape(B, -1) != 0).any(dim=1).tolist()
@@ -329,14 +348,14 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
         pack = self._prepare(dev)
         B, L, C = x.shape
         assert C == self.in_channels
-        ck, cvt, ca_batch = self._context_kv(pack, context["img_crossattn"])
-        Mctx = context["img_crossattn"].shape[1]
+        ck, cvt, ca_batch = self._context_kv(pack, context[self._ctx_key])
+        Mctx = context[self._ctx_key].shape[1]
         xin = x if _step is not None else x.detach().float().contiguous()
         t = timesteps.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
         if t.numel() == 1 and B > 1:
             t = t.expand(B).contiguous()
-        vec = context["img_vector"].detach().float().contiguous()
-        pooled = self._pooled(pack, vec) if vec is context["img_vector"] or vec.data_ptr() == context["img_vector"].data_ptr() else None
+        vec = context[self._vec_key].detach().float().contiguous()
+        pooled = self._pooled(pack, vec) if vec is context[self._vec_key] or vec.data_ptr() == context[self._vec_key].data_ptr() else None
         xyz = context["fps-xyz"].detach().float().contiguous() if self._stage2 else None
         out = torch.empty((B, L, self.out_channels), dtype=torch.float32, device=dev) if _step is None else None
         Lib = ops.lib()
@@ -376,7 +395,7 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
         held = getattr(self, "_ctx_bufs", None) or {}
         out = {}
         for name, t in context.items():
-            want = torch.float32 if name in ("img_vector", "fps-xyz") else t.dtype
+            want = torch.float32 if name in (self._vec_key, "fps-xyz") else t.dtype
             buf = held.get(name)
             if buf is None or buf.shape != t.shape or buf.dtype != want or buf.device != t.device:
                 buf = torch.empty(t.shape, dtype=want, device=t.device)
@@ -390,16 +409,16 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
         conditioning tokens (refreshed here, in place when the shapes are those of the previous call), the number of batch items
         that skip the cross-attention, the resident conditioning vectors -- all by address.  None: nothing to replay against yet."""
         B, L, _ = shape
-        tok = context["img_crossattn"]
+        tok = context[self._ctx_key]
         pack = self._prepare(tok.device)
         ck, cvt, ca_batch = self._context_kv(pack, tok)
         if pack.get("ws") is None or pack["ws_key"] != (B, L, tok.shape[1]):
             return None
         sig = [tuple(shape), n, bool(cfg), float(cfg_scale), pack["ws"].data_ptr(), ck.data_ptr(), cvt.data_ptr(), ca_batch]
-        vec = context["img_vector"]
+        vec = context[self._vec_key]
         if self.pooled_once and vec.dtype == torch.float32 and vec.is_contiguous():
             sig.append(self._pooled(pack, vec).data_ptr())     # (refreshed in place for this call's vector)
-        for name in ("img_vector",) + (("fps-xyz",) if self._stage2 else ()):
+        for name in (self._vec_key,) + (("fps-xyz",) if self._stage2 else ()):
             t = context[name]
             if t.dtype != torch.float32 or not t.is_contiguous():
                 return None   # (forward() would hand the kernels a temporary copy)

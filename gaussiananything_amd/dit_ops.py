@@ -51,6 +51,11 @@ class GaAttentionPlan(ctypes.Structure):
     _fields_ = [(n, i32) for n in ("nw", "ks", "knorm", "tps", "queries_per_wg", "fuses_q", "grid_x", "grid_y", "grid_z", "lds_bytes")]
 
 
+class GaAttentionShortPlan(ctypes.Structure):
+    """include/ga_dit.h: GaAttentionShortPlan (what ga_attention_short_bf16 launches; ga_attention_short_plan)"""
+    _fields_ = [(n, i32) for n in ("queries_per_wg", "key_tiles", "fuses_q", "grid_x", "grid_y", "grid_z", "lds_bytes")]
+
+
 class GaAttentionHdPlan(ctypes.Structure):
     """include/ga_dit.h: GaAttentionHdPlan (what ga_attention_hd_bf16 launches; ga_attention_hd_plan / ga_attention_hd_instances)"""
     _fields_ = [(n, i32) for n in ("family", "hd16", "hdp", "config", "qf", "nw", "ks", "forced", "queries_per_wg", "grid_x", "grid_y",
@@ -74,7 +79,7 @@ class GaDitBlockWeights(ctypes.Structure):
     _fields_ = [(n, c_p) for n in (
         "prenorm_ca_w", "ca_q_w", "ca_q_w_prenorm", "ca_kv_w", "ca_q_norm_w", "ca_k_norm_w", "ca_out_w", "ca_out_b", "norm1_w", "qkv_w",
         "qkv_b", "q_norm_w", "k_norm_w", "proj_w", "proj_b", "norm2_w", "fc1_w", "fc1_b", "fc2_w", "fc2_b",
-        "scale_shift_table")]
+        "scale_shift_table", "ctx_norm_w")]
 
 
 class GaDitModel(ctypes.Structure):
@@ -83,7 +88,8 @@ class GaDitModel(ctypes.Structure):
                     "t_mlp0_w", "t_mlp0_b", "t_mlp2_w", "t_mlp2_b", "pool_ln_w", "pool_ln_b", "pool_w", "pool_b",
                     "adaln_w", "adaln_b", "xe_fc1_w", "xe_fc1_b", "xe_fc2_w", "xe_fc2_b", "xyz_w", "xyz_b",
                     "final_table", "final_w", "final_b")] + [("blocks", ctypes.POINTER(GaDitBlockWeights)),
-                                                              ("gemm_weights_tiled", i32)]
+                                                              ("gemm_weights_tiled", i32), ("block_order", i32),
+                                                              ("final_adaln_w", c_p), ("final_adaln_b", c_p)]
 
 
 class GaDitSamplerStep(ctypes.Structure):
@@ -115,7 +121,8 @@ class GaDitForwardArgs(ctypes.Structure):
 DIT_EXPORTS = ("ga_gemm_bf16", "ga_attention_bf16", "ga_attention_hd_bf16", "ga_head_rmsnorm_bf16", "ga_rmsnorm_modulate", "ga_small_linear", "ga_dit_workspace_bytes",
                "ga_dit_cache_context", "ga_dit_forward", "ga_dit_pooled_vector", "ga_dit_shift_bias", "ga_dit_sampler_advance", "ga_ode_dopri5_stage", "ga_ode_dopri5_finish",
                "ga_dit_version", "ga_gemm_splitk_workspace_bytes", "ga_gemm_splitk_mode", "ga_gemm_plan", "ga_gemm_instances",
-               "ga_attention_plan", "ga_attention_instances", "ga_attention_hd_plan", "ga_attention_hd_instances")
+               "ga_attention_plan", "ga_attention_instances", "ga_attention_hd_plan", "ga_attention_hd_instances",
+               "ga_dit_context_scratch_bytes", "ga_dit_cache_context_ws", "ga_attention_short_bf16", "ga_attention_short_plan")
 _ERR = {-1: "GA_DIT_ERR_NULL_ARG", -2: "GA_DIT_ERR_BAD_SHAPE", -4: "GA_DIT_ERR_LAUNCH"}
 _bound = False
 
@@ -134,6 +141,14 @@ def lib():
             getattr(L, name).restype = ctypes.c_int
         L.ga_dit_cache_context.restype = ctypes.c_int
         L.ga_dit_cache_context.argtypes = [ctypes.POINTER(GaDitModel), i32, i32, c_p, c_p, c_p, c_p]
+        L.ga_attention_short_bf16.restype = ctypes.c_int
+        L.ga_attention_short_bf16.argtypes = [ctypes.POINTER(GaAttentionArgs), c_p]
+        L.ga_attention_short_plan.restype = ctypes.c_int
+        L.ga_attention_short_plan.argtypes = [ctypes.POINTER(GaAttentionArgs), ctypes.POINTER(GaAttentionShortPlan)]
+        L.ga_dit_context_scratch_bytes.restype = ctypes.c_size_t
+        L.ga_dit_context_scratch_bytes.argtypes = [ctypes.POINTER(GaDitModel), i32, i32]
+        L.ga_dit_cache_context_ws.restype = ctypes.c_int
+        L.ga_dit_cache_context_ws.argtypes = [ctypes.POINTER(GaDitModel), i32, i32, c_p, c_p, c_p, c_p, ctypes.c_size_t, c_p]
         L.ga_dit_forward.restype = ctypes.c_int
         L.ga_dit_forward.argtypes = [ctypes.POINTER(GaDitModel), ctypes.POINTER(GaDitForwardArgs), c_p]
         L.ga_head_rmsnorm_bf16.restype = ctypes.c_int
@@ -233,6 +248,13 @@ def attention_plan(args):
     """GaAttentionArgs -> the GaAttentionPlan ga_attention_bf16 would launch for it (no GPU needed; raises on invalid arguments)"""
     plan = GaAttentionPlan()
     check(lib().ga_attention_plan(ctypes.byref(args), ctypes.byref(plan)), "ga_attention_plan")
+    return plan
+
+
+def attention_short_plan(args):
+    """GaAttentionArgs -> the GaAttentionShortPlan ga_attention_short_bf16 would launch for it (no GPU needed; raises on invalid arguments)"""
+    plan = GaAttentionShortPlan()
+    check(lib().ga_attention_short_plan(ctypes.byref(args), ctypes.byref(plan)), "ga_attention_short_plan")
     return plan
 
 

@@ -203,6 +203,25 @@ int ga_attention_plan(const GaAttentionArgs *args, GaAttentionPlan *plan);
  * zero) and returns how many there are. */
 int ga_attention_instances(GaAttentionPlan *out, int32_t capacity);
 
+/* The same attention for SHORT key lists, Lk <= 128 (the 77 caption tokens of the text denoisers' cross-attention), head dim 64:
+ * attention_short_kernel (dit_attention_short.hip) stages K and V^T of a head once, runs one S = Q K^T pass over at most 8 key
+ * fragments with the key columns >= Lk masked, a one-pass softmax with the true row maximum (no rescale, no merge), then P V.  Same
+ * arguments and layouts as ga_attention_bf16, q given or projected inside the workgroup (qp_*: the semantics of the 64-query
+ * configuration's projection, the projected q rounded to bf16); k_norm_weight must be NULL.  It is NOT one of ga_attention_bf16's
+ * instances: nothing dispatches to it by shape -- ga_dit_forward calls it for the cross-attention of block order 1 when
+ * ctx_tokens <= 128 (environment switch GA_DIT_SHORT_CA). */
+typedef struct GaAttentionShortPlan {
+    int32_t queries_per_wg;   /* 64: four waves of 16 query rows                                                */
+    int32_t key_tiles;        /* 64-key tiles staged per workgroup: 1 or 2                                      */
+    int32_t fuses_q;          /* 1: this launch computes the q projection itself (GaAttentionArgs.qp_a)         */
+    int32_t grid_x, grid_y, grid_z;   /* heads * batch, query tiles, 1                                          */
+    int32_t lds_bytes;        /* 16 KiB per key tile (K + V^T); + 48 KiB with fuses_q: the ring of the projection's W / A slices */
+} GaAttentionShortPlan;
+int ga_attention_short_bf16(const GaAttentionArgs *args, void *stream);
+/* Host-only like ga_attention_plan: the error code ga_attention_short_bf16 would return (Lk > 128, k_norm_weight, and every
+ * misalignment ga_attention_plan refuses), or 0 and the launch geometry. */
+int ga_attention_short_plan(const GaAttentionArgs *args, GaAttentionShortPlan *plan);
+
 /* The same attention for head dims OTHER than 64 (head_dim % 8 == 0, <= 128): DiT-PixArt-PCD-CLAY-XL of the reference registry has 16
  * heads of 72 (/root/reference/dit/dit_i23d.py:1526-1535, 1677).  q, k, v row-major: row (b, i) of q starts at q + (b*Lq + i)*q_stride +
  * h*head_dim (k, v: b*Lk + j); q and k ALREADY carry their per-head RMSNorm (ga_head_rmsnorm_bf16); softmax scale head_dim^-1/2.
@@ -309,6 +328,10 @@ typedef struct GaDitBlockWeights {
     const ga_bf16 *fc2_w;                /* [D, 4D]                                     */
     const float *fc2_b;                  /* [D]                                         */
     const float *scale_shift_table;      /* [6, D]                                      */
+    /* Text models (dit/dit_trilatent.py, PixelArtTextCondDiTBlock.attention_y_norm), NULL = none: [context_dim] weight of an RMSNorm
+     * (eps 1e-5) every block applies to the context tokens before its to_k / to_v: ga_dit_cache_context_ws projects K | V^T of this
+     * block from RMSNorm(ctx) * ctx_norm_w.  prenorm_ca_w / ca_* then carry prenorm_ca_text / cross_attn.*. */
+    const float *ctx_norm_w;
 } GaDitBlockWeights;
 
 typedef struct GaDitModel {
@@ -327,6 +350,16 @@ typedef struct GaDitModel {
     int32_t gemm_weights_tiled;                         /* 1: every bf16 [N, K] weight that goes through ga_gemm_bf16 (block weights,
                                                            xe_fc2_w) is stored tiled, see GaGemmArgs.w_tiled; the small-linear
                                                            weights (t_mlp*, pool_w, adaln_w) stay row-major */
+    /* ---- the caption-conditioned twins (DiT_PCD_PixelArt, DiT_PCD_PixelArt_tofeat: /root/reference/dit/dit_trilatent.py:262-419);
+     *      every field 0 / NULL = the image models above, launch for launch ---- */
+    int32_t block_order;                                /* 0: cross-attention, self-attention, MLP (ImageCondDiTBlockPixelArtRMSNormClayLRM);
+                                                           1: self-attention, cross-attention, MLP (PixelArtTextCondDiTBlock, dit_models_xformers.py:357-376).
+                                                           Order 1 is built for heads of 64 only: any other head dim (the registry's unreleased
+                                                           DiT-PCD-XL-stage2-xyz2feat, 16 x 72) is REFUSED with GA_DIT_ERR_BAD_SHAPE before anything is enqueued */
+    const ga_bf16 *final_adaln_w; const float *final_adaln_b;   /* [2D, D], [2D]  final_layer.adaLN_modulation.1, row-major.  When set the final layer is
+                                                           the reference's FinalLayer (dit_models_xformers.py:993-1016): (shift | scale) = Linear(SiLU(t)) per batch item
+                                                           -- one small-linear launch -- in place of final_table + t; final_table is not read.  The fused sampler
+                                                           step (GaDitSamplerStep) works on it unchanged.  pool_* then carry cap_embedder.{0,1} and img_vector the caption vector */
 } GaDitModel;
 
 /* Optional sampler step fused into the final layer (GaDitForwardArgs.step): the Euler update of the reference's fixed-grid
@@ -383,6 +416,13 @@ size_t ga_dit_workspace_bytes(const GaDitModel *model, int32_t batch, int32_t to
  * caller beforehand: only the first M keys of every row are written). */
 int ga_dit_cache_context(const GaDitModel *model, int32_t batch, int32_t ctx_tokens, const ga_bf16 *img_crossattn,
                          ga_bf16 *ca_k, ga_bf16 *ca_vt, void *stream);
+
+/* The same with a scratch for the normalised context of models whose blocks carry ctx_norm_w: ga_dit_context_scratch_bytes() bytes
+ * (0 for a model without ctx_norm_w), 256-byte aligned.  ga_dit_cache_context is this call without a scratch: it returns
+ * GA_DIT_ERR_NULL_ARG for a model that needs one.  Once per conditioning, not hot: a norm pass per block, then the same GEMM. */
+size_t ga_dit_context_scratch_bytes(const GaDitModel *model, int32_t batch, int32_t ctx_tokens);
+int ga_dit_cache_context_ws(const GaDitModel *model, int32_t batch, int32_t ctx_tokens, const ga_bf16 *ctx, ga_bf16 *ca_k, ga_bf16 *ca_vt,
+                            void *scratch, size_t scratch_bytes, void *stream);
 
 int ga_dit_forward(const GaDitModel *model, const GaDitForwardArgs *args, void *stream);
 
