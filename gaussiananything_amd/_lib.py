@@ -74,9 +74,32 @@ class GaTsdfFrame(ctypes.Structure):
                 ("extrinsic", ctypes.c_double * 16), ("pose", ctypes.c_double * 16), ("depth_sampling_stride", ctypes.c_int32)]
 
 
+class GaFpsArgs(ctypes.Structure):
+    """include/ga_pointcloud.h: GaFpsArgs"""
+    _fields_ = [("batch", ctypes.c_int32), ("num_points", ctypes.c_int32), ("num_samples", ctypes.c_int32),
+                ("points", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("start_idx", ctypes.c_void_p),
+                ("out_idx", ctypes.c_void_p), ("out_points", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("workspace_bytes", ctypes.c_size_t)]
+
+
+class GaFpsPlan(ctypes.Structure):
+    """include/ga_pointcloud.h: GaFpsPlan"""
+    _fields_ = [("variant", ctypes.c_int32), ("threads", ctypes.c_int32), ("points_per_lane", ctypes.c_int32)]
+
+
+class GaNearestArgs(ctypes.Structure):
+    """include/ga_pointcloud.h: GaNearestArgs"""
+    _fields_ = [("batch", ctypes.c_int32), ("num_query", ctypes.c_int32), ("num_target", ctypes.c_int32),
+                ("query", ctypes.c_void_p), ("target", ctypes.c_void_p), ("query_lengths", ctypes.c_void_p),
+                ("target_lengths", ctypes.c_void_p), ("out_dist2", ctypes.c_void_p), ("out_idx", ctypes.c_void_p)]
+
+
+GA_FPS_VARIANT_REGISTER, GA_FPS_VARIANT_STREAMING = 0, 1
+
 EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspace_layout2", "ga_surfel_forward", "ga_surfel_postprocess",
            "ga_surfel_backward", "ga_surfel_backward_scratch_bytes",
-           "ga_tsdf_integrate", "ga_tsdf_mesh_scratch_bytes", "ga_tsdf_mesh_count", "ga_tsdf_mesh_emit", "ga_mesh_write_obj", "ga_mesh_cluster_labels")
+           "ga_tsdf_integrate", "ga_tsdf_mesh_scratch_bytes", "ga_tsdf_mesh_count", "ga_tsdf_mesh_emit", "ga_mesh_write_obj", "ga_mesh_cluster_labels",
+           "ga_pc_fps", "ga_pc_fps_plan", "ga_pc_fps_workspace_bytes", "ga_pc_nearest")
 
 _lib = None
 
@@ -132,6 +155,14 @@ def lib():
         L.ga_tsdf_mesh_emit.restype = ctypes.c_int
         L.ga_tsdf_mesh_emit.argtypes = [ctypes.POINTER(GaTsdfVolume), ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_int64,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.ga_pc_fps.restype = ctypes.c_int
+        L.ga_pc_fps.argtypes = [ctypes.POINTER(GaFpsArgs), ctypes.c_void_p]
+        L.ga_pc_fps_plan.restype = ctypes.c_int
+        L.ga_pc_fps_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GaFpsPlan)]
+        L.ga_pc_fps_workspace_bytes.restype = ctypes.c_size_t
+        L.ga_pc_fps_workspace_bytes.argtypes = [ctypes.c_int32] * 3
+        L.ga_pc_nearest.restype = ctypes.c_int
+        L.ga_pc_nearest.argtypes = [ctypes.POINTER(GaNearestArgs), ctypes.c_void_p]
         _lib = L
     return _lib
 

@@ -8,6 +8,8 @@
   * decoded surfels: ``[1, N, 13]`` float32 ``.npy`` (:1475).
   * what the engine leaves for viewers: coloured point clouds as binary glTF + PLY (:1452-1464, :1742-1753), meshes as GLB / OBJ
     (utils/mesh_util.py:113-136), the surfels as a 2DGS-style PLY (nsr/gs_surfel.py:206-265).
+  * the evaluation hand-off ``fps-4096.ply`` (scripts/save_pcd_from_gs.py:148-185): ``export_fps_points`` -- the one function here
+    that needs the GPU (farthest point sampling, ``gaussiananything_amd.pointcloud``).
 
 ``gaussiananything_amd.cascade`` keeps the tensors on the device; these functions reproduce the file-based hand-off for
 interoperability with the reference scripts.
@@ -267,6 +269,29 @@ def export_stage1_point_cloud(xyz, save_dir, name_prefix):
     write_glb(glb, v @ rotation_matrix_x(-90).T, colors=np.ones_like(v) * 0.1)
     save_points_ply(ply, v)
     return glb, ply
+
+
+def export_fps_points(gaussians, path, K=4096, opacity_thres=0.005):
+    """The evaluation hand-off of generated surfels (scripts/save_pcd_from_gs.py:161-185): drop the surfels whose opacity is below
+    ``opacity_thres`` ("official threshold"), take ``K`` farthest points of the remaining centres starting from index 0
+    (``pytorch3d.ops.sample_farthest_points(points[None], K=K)`` there, the HIP kernel behind ``pointcloud.sample_farthest_points``
+    here -- GPU only, no fallback) and write them as the vertex-only PLY ``fps-{K}.ply`` is.  ``gaussians``: [1, N, 13] or [N, 13]
+    array or tensor (xyz, opacity, ...).  As in the reference, a set with fewer than ``K`` surviving surfels still yields ``K``
+    vertices, the missing ones zero.  Returns the points, float32 [K, 3]."""
+    import torch
+    from .pointcloud import sample_farthest_points
+    g = gaussians.detach() if hasattr(gaussians, "detach") else torch.from_numpy(np.asarray(gaussians, dtype=np.float32))
+    if g.dim() == 3 and g.shape[0] == 1:
+        g = g[0]
+    if g.dim() != 2 or g.shape[-1] != 13:
+        raise ValueError("expected [1, N, 13] surfel Gaussians")
+    g = g.to("cuda", torch.float32) if g.device.type != "cuda" else g.float()
+    kept = g[~(g[:, 3] < opacity_thres), :3]
+    if kept.shape[0] == 0:
+        raise ValueError("no surfel reaches the opacity threshold")
+    pts = sample_farthest_points(kept[None], K=K)[0][0].cpu().numpy()
+    save_points_ply(path, pts)
+    return pts
 
 
 def save_glb(pointnp_px3, facenp_fx3, colornp_px3, fpath):
