@@ -22,7 +22,7 @@ PCD_SCALING_FACTOR = 0.45  # sgm/configs/stage2-i23d.yaml:55-57 -> PCD_Scaler (s
 
 @torch.no_grad()
 def sample(model, cond, uc, shape, batch_size=1, cfg_scale=4.0, seed=42, num_steps=250, sampling_method="dopri5",
-           transport_sampler=None, noise_dtype=torch.bfloat16, stats=None, dedup_noop_cfg=True, **ode_kwargs):
+           transport_sampler=None, noise_dtype=torch.bfloat16, stats=None, dedup_noop_cfg=True, sde=None, **ode_kwargs):
     """``FlowMatchingEngine.sample`` (flow_matching_trainer.py:700-744): CPU-seeded noise, CFG batch = [cond | uncond],
     ``sample_ode(num_steps=250, cfg=True)`` (dopri5 by default, as upstream), last state, conditional half.
 
@@ -34,10 +34,19 @@ def sample(model, cond, uc, shape, batch_size=1, cfg_scale=4.0, seed=42, num_ste
     release's stage 2, ``stage2_conditioning``), both halves of the CFG batch are the same sequence, ``forward_with_cfg``
     returns ``uncond + s * (cond - uncond) = cond`` and the two halves of the ODE state stay equal (dopri5's RMS norm over
     the doubled state equals that over one half): the denoiser is evaluated on the conditional half alone -- the same
-    numbers up to the GEMM tile shapes chosen for the smaller batch, half the work."""
+    numbers up to the GEMM tile shapes chosen for the smaller batch, half the work.
+
+    ``sde``: a dict of ``Sampler.sample_sde`` keywords (may be empty) samples this stage with the SDE sampler instead of
+    ``sample_ode`` -- ``num_steps`` and ``seed`` default to this call's, ``sampling_method`` / ``ode_kwargs`` are then not used;
+    ``stats`` receives nfe / steps / sde=True."""
     if transport_sampler is None:
         transport_sampler = Sampler(create_transport("GVP", "velocity", None, None, None, snr_type="uniform"))
-    sample_fn = transport_sampler.sample_ode(sampling_method=sampling_method, num_steps=num_steps, cfg=True, **ode_kwargs)
+    if sde is not None:
+        sample_fn = transport_sampler.sample_sde(**dict({"num_steps": num_steps, "seed": seed}, **sde))
+        last = "last_sde"
+    else:
+        sample_fn = transport_sampler.sample_ode(sampling_method=sampling_method, num_steps=num_steps, cfg=True, **ode_kwargs)
+        last = "last_ode"
     dev = next(model.parameters()).device
     torch.manual_seed(seed)
     zs = torch.randn(batch_size, *shape).to(dev)
@@ -48,13 +57,13 @@ def sample(model, cond, uc, shape, batch_size=1, cfg_scale=4.0, seed=42, num_ste
             return model.forward(x, t, context)
         samples = sample_fn(zs, getattr(model, "forward_cond", cond_only), context=dict(cond), cfg_scale=cfg_scale)[-1]
         if stats is not None:
-            stats.update(getattr(getattr(transport_sampler, "last_ode", None), "last_stats", {}) or {}, noop_cfg_dedup=True)
+            stats.update(getattr(getattr(transport_sampler, last, None), "last_stats", {}) or {}, noop_cfg_dedup=True)
         return samples
     c_out = {k: torch.cat((cond[k], uc[k]), 0) for k in cond}
     zs = torch.cat([zs, zs], 0)
     samples = sample_fn(zs, model.forward_with_cfg, context=c_out, cfg_scale=cfg_scale)[-1]
     if stats is not None:   # function evaluations / accepted / rejected steps of this stage's ODE solve
-        stats.update(getattr(getattr(transport_sampler, "last_ode", None), "last_stats", {}) or {})
+        stats.update(getattr(getattr(transport_sampler, last, None), "last_stats", {}) or {})
     samples, _ = samples.chunk(2, dim=0)
     return samples
 

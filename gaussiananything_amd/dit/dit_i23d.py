@@ -600,6 +600,117 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
             stats.update(nfe=evals_before, steps=0, rejected=0, graph=True, device_loop=True)
         return out.clone()
 
+    def sample_sde_device(self, x0, coef, context, method="Euler", last_step="Mean", cfg_scale=1.0, cfg=True, seed=0, noise=None,
+                          noise_out=None):
+        with self._exclusive(x0.device):
+            return self._sample_sde_device(x0, coef, context, method, last_step, cfg_scale, cfg, seed, noise, noise_out)
+
+    @torch.no_grad()
+    def _sample_sde_device(self, x0, coef, context, method, last_step, cfg_scale, cfg, seed, noise, noise_out):
+        """The reference's SDE sampling loop (``Sampler.sample_sde``, transport/transport.py:322-382: the stepper of
+        transport/integrators.py:8-75 and one last step) with every step on the device (csrc/ode_sde.hip, GaSdeStep in
+        include/ga_dit.h): a step is the function evaluation with the guided velocity leaving through the final-layer kernel, the
+        Euler-Maruyama update (``method="Euler"``) or Heun's three phases around two evaluations (``"Heun"``) with the noise drawn
+        inside the kernel, and the one-thread advance -- captured into ONE HIP graph and replayed for every interval, then the last
+        step eagerly.  The step index, the coefficient table ``coef`` ([intervals + 1, GA_SDE_COEF_STRIDE] fp32, built by
+        ``transport.sampler.sde_coefficients``), the seed and the initial state are device data rewritten per call: the captured step
+        serves any seed, diffusion form and norm, and every replay draws fresh noise.  ``cfg``: the state is a doubled CFG batch whose
+        halves take the same noise.  ``noise`` [intervals, n_draw]: normals to use instead; ``noise_out`` [intervals, n_draw]: receives
+        the normals every step used.  Returns [intervals + 1, *x0.shape] fp32: slot k is the state after step k, the last slot the
+        last step's output.  Bit-identical to the eager loop of ``transport/sampler.py`` on the same normals."""
+        if self.out_channels != self.in_channels:
+            raise ValueError("the device-resident SDE sampler needs a velocity of the state's shape (learn_sigma=False)")
+        phases = {"Euler": (ops.GA_SDE_EM,), "Heun": (ops.GA_SDE_HEUN_PERTURB, ops.GA_SDE_HEUN_PREDICT, ops.GA_SDE_HEUN_CORRECT)}
+        lasts = {"Mean": ops.GA_SDE_LAST_MEAN, "Tweedie": ops.GA_SDE_LAST_TWEEDIE, "Euler": ops.GA_SDE_LAST_EULER, None: ops.GA_SDE_LAST_NONE}
+        if method not in phases or last_step not in lasts:
+            raise ValueError(f"SDE sampler: method {method!r} / last step {last_step!r} (have {tuple(phases)} / {tuple(lasts)})")
+        dev = x0.device
+        ni = coef.shape[0] - 1
+        if coef.dim() != 2 or coef.shape[1] != ops.GA_SDE_COEF_STRIDE or ni < 1:
+            raise ValueError("coef is the [intervals + 1, GA_SDE_COEF_STRIDE] table of sde_coefficients")
+        B, n = x0.shape[0], x0.numel()
+        nd = n // 2 if cfg else n
+        if cfg and B % 2:
+            raise ValueError("a CFG state holds the conditional and the unconditional half")
+        for name, t in (("noise", noise), ("noise_out", noise_out)):
+            if t is not None and (t.numel() != ni * nd or t.shape[0] != ni):
+                raise ValueError(f"{name} is [intervals = {ni}, n_draw = {nd}]")
+        Lib = ops.lib()
+        context = self._resident_context(context)
+        key = (method, ni + 1, noise is not None, noise_out is not None)
+        sig = self._replay_signature(context, x0.shape, ni + 1, cfg, cfg_scale)
+        held = getattr(self, "_sde_replay", None)
+        if sig is not None and held is not None and held["sig"] == (sig, key):     # buffers and captured step of an earlier call
+            st = held
+        else:
+            y = torch.empty(tuple(x0.shape), dtype=torch.float32, device=dev)
+            st = {"sig": None, "y": y, "vel": torch.empty_like(y), "k1": torch.empty_like(y), "xhat": torch.empty_like(y),
+                  "out": torch.empty((ni + 1,) + tuple(y.shape), dtype=torch.float32, device=dev),
+                  "counter": torch.zeros(1, dtype=torch.int32, device=dev), "tvec": torch.empty(B, dtype=torch.float32, device=dev),
+                  "coef": torch.empty((ni + 1, ops.GA_SDE_COEF_STRIDE), dtype=torch.float32, device=dev),
+                  "seed": torch.zeros(1, dtype=torch.int64, device=dev),
+                  "noise": torch.empty((ni, nd), dtype=torch.float32, device=dev) if noise is not None else None,
+                  "nout": torch.empty(nd, dtype=torch.float32, device=dev) if noise_out is not None else None,
+                  "graph": None, "keep": tuple(context.values())}
+        y, vel, out, counter, tvec, cf = (st[q] for q in ("y", "vel", "out", "counter", "tvec", "coef"))
+        cf.copy_(coef.detach().to(torch.float32))
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        st["seed"].copy_(torch.tensor([seed - (1 << 64) if seed >> 63 else seed], dtype=torch.int64))
+        if noise is not None:
+            st["noise"].copy_(noise.detach().reshape(ni, nd))
+        sde = ops.GaSdeStep(n, B, ni, 1 if cfg else 0, y.data_ptr(), vel.data_ptr(), st["k1"].data_ptr(), st["xhat"].data_ptr(),
+                            out.data_ptr(), counter.data_ptr(), tvec.data_ptr(), cf.data_ptr(), st["seed"].data_ptr(),
+                            st["noise"].data_ptr() if noise is not None else None, st["nout"].data_ptr() if noise_out is not None else None)
+        vstep = ops.GaDitSamplerStep(float(cfg_scale), 1 if cfg else 0, None, None, None, 0, None, vel.data_ptr())
+
+        def phase(p):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            ops.check(Lib.ga_sde_step(ctypes.byref(sde), p, stream), "ga_sde_step")
+
+        def one_step():     # a single chain of launches
+            if method == "Euler":
+                self.forward(y, tvec, context, _step=vstep)
+                phase(ops.GA_SDE_EM)
+            else:
+                phase(ops.GA_SDE_HEUN_PERTURB)
+                self.forward(st["xhat"], tvec, context, _step=vstep)
+                phase(ops.GA_SDE_HEUN_PREDICT)
+                self.forward(y, tvec, context, _step=vstep)
+                phase(ops.GA_SDE_HEUN_CORRECT)
+            phase(ops.GA_SDE_ADVANCE)
+
+        def reset():
+            y.copy_(x0.detach().float())
+            counter.zero_()
+            tvec.copy_(cf[0, ops.GA_SDE_C_T].expand(B))
+
+        reset()
+        if st["graph"] is None:
+            cur = torch.cuda.current_stream(dev)
+            side = torch.cuda.Stream(dev)
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):   # warm-up outside the capture: lazy initialisation, workspace sizing, K/V caches
+                one_step()
+            cur.wait_stream(side)
+            reset()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                one_step()
+            reset()   # (capture does not execute; the state is as before)
+            st["graph"] = graph
+            # (the signature exists once the first evaluation has sized the workspace and cached the K / V)
+            sig = self._replay_signature(context, y.shape, ni + 1, cfg, cfg_scale)
+            st["sig"] = (sig, key) if sig is not None else None
+            self._sde_replay = st
+        for k in range(ni):
+            st["graph"].replay()
+            if noise_out is not None:
+                noise_out[k].reshape(-1).copy_(st["nout"])
+        if last_step is not None:
+            self.forward(y, tvec, context, _step=vstep)      # (ADVANCE left t1 in tvec)
+        phase(lasts[last_step])
+        return out.clone()
+
 
 class DiT_I23D_PCD_PixelArt_noclip_clay_stage2(DiT_I23D_PCD_PixelArt_noclip):
     """Stage-2 (KL feature) denoiser conditioned on the stage-1 point cloud (dit_i23d.py:664-750)."""

@@ -104,6 +104,21 @@ class GaOdeDopri5(ctypes.Structure):
                 ("ctl", c_p), ("t_grid", c_p), ("out", c_p), ("ctl_words", ctypes.c_int64)]
 
 
+class GaSdeStep(ctypes.Structure):
+    """include/ga_dit.h: GaSdeStep"""
+    _fields_ = [("n", ctypes.c_int64), ("batch", i32), ("num_intervals", i32), ("cfg_pairs", i32), ("state", c_p), ("velocity", c_p),
+                ("k1", c_p), ("xhat", c_p), ("traj", c_p), ("counter", c_p), ("timesteps", c_p), ("coef", c_p), ("seed", c_p),
+                ("noise", c_p), ("noise_out", c_p)]
+
+
+# phases of ga_sde_step and the columns of a GaSdeStep.coef row (include/ga_dit.h)
+(GA_SDE_EM, GA_SDE_HEUN_PERTURB, GA_SDE_HEUN_PREDICT, GA_SDE_HEUN_CORRECT, GA_SDE_LAST_MEAN, GA_SDE_LAST_TWEEDIE, GA_SDE_LAST_EULER,
+ GA_SDE_LAST_NONE, GA_SDE_ADVANCE) = range(9)
+(GA_SDE_C_T, GA_SDE_C_DT, GA_SDE_C_SQRT_DT, GA_SDE_C_W, GA_SDE_C_G, GA_SDE_C_R, GA_SDE_C_VAR, GA_SDE_C_T2, GA_SDE_C_W2, GA_SDE_C_R2,
+ GA_SDE_C_VAR2, GA_SDE_C_HALF_DT, GA_SDE_C_ALPHA, GA_SDE_C_SIG2A) = range(14)
+GA_SDE_COEF_STRIDE = 16
+
+
 # indices into GaOdeDopri5.ctl (include/ga_dit.h)
 (GA_ODE_T, GA_ODE_DT, GA_ODE_SUMSQ, GA_ODE_ATOL, GA_ODE_RTOL, GA_ODE_DONE, GA_ODE_STEPS, GA_ODE_REJECTED, GA_ODE_ACCEPT, GA_ODE_TA,
  GA_ODE_TB, GA_ODE_DT_USED, GA_ODE_JNEXT, GA_ODE_JBEG, GA_ODE_JCOUNT, GA_ODE_ERROR, GA_ODE_RATIO) = range(17)
@@ -122,7 +137,7 @@ DIT_EXPORTS = ("ga_gemm_bf16", "ga_attention_bf16", "ga_attention_hd_bf16", "ga_
                "ga_dit_cache_context", "ga_dit_forward", "ga_dit_pooled_vector", "ga_dit_shift_bias", "ga_dit_sampler_advance", "ga_ode_dopri5_stage", "ga_ode_dopri5_finish",
                "ga_dit_version", "ga_gemm_splitk_workspace_bytes", "ga_gemm_splitk_mode", "ga_gemm_plan", "ga_gemm_instances",
                "ga_attention_plan", "ga_attention_instances", "ga_attention_hd_plan", "ga_attention_hd_instances",
-               "ga_dit_context_scratch_bytes", "ga_dit_cache_context_ws", "ga_attention_short_bf16", "ga_attention_short_plan")
+               "ga_dit_context_scratch_bytes", "ga_dit_cache_context_ws", "ga_attention_short_bf16", "ga_attention_short_plan", "ga_sde_step", "ga_sde_step_check")
 _ERR = {-1: "GA_DIT_ERR_NULL_ARG", -2: "GA_DIT_ERR_BAD_SHAPE", -4: "GA_DIT_ERR_LAUNCH"}
 _bound = False
 
@@ -163,6 +178,10 @@ def lib():
         L.ga_ode_dopri5_stage.argtypes = [ctypes.POINTER(GaOdeDopri5), i32, c_p]
         L.ga_ode_dopri5_finish.restype = ctypes.c_int
         L.ga_ode_dopri5_finish.argtypes = [ctypes.POINTER(GaOdeDopri5), c_p]
+        L.ga_sde_step.restype = ctypes.c_int
+        L.ga_sde_step.argtypes = [ctypes.POINTER(GaSdeStep), i32, c_p]
+        L.ga_sde_step_check.restype = ctypes.c_int
+        L.ga_sde_step_check.argtypes = [ctypes.POINTER(GaSdeStep), i32]
         L.ga_gemm_splitk_workspace_bytes.restype = ctypes.c_size_t
         L.ga_gemm_splitk_workspace_bytes.argtypes = [i32, i32]
         L.ga_gemm_splitk_mode.restype = ctypes.c_int

@@ -1,8 +1,8 @@
 """The sampling entry of the denoise half, cut down to what the released models use, plus the hook that gives the REFERENCE'S OWN
 ``transport`` package the device-resident integrators.
 
-The reference's ``transport/*.py`` (path plans, score / noise parametrisations, SDE samplers) is device-agnostic host Python and is
-not rebuilt here: a deployment keeps importing it and calls ``bind_reference_transport(transport.integrators)`` once
+The reference's ``transport/*.py`` (path plans, score / noise parametrisations, reverse-time and likelihood sampling) is device-agnostic
+host Python and is not rebuilt here: a deployment keeps importing it and calls ``bind_reference_transport(transport.integrators)`` once
 (INTEGRATION.md section 3).  After that ``transport.integrators.ode.sample`` (/root/reference/transport/integrators.py:100-119)
 hands fixed-grid Euler and dopri5 integrations of a HIP denoiser to this package instead of torchdiffeq; everything else of the
 reference's transport code runs unchanged.
@@ -10,11 +10,17 @@ reference's transport code runs unchanged.
 For ``bench.py`` / the tests / ``cascade.sample`` -- which must run on a GPU box that has no reference tree -- this module carries the
 one configuration the release uses (sgm/configs/stage2-i23d.yaml: velocity prediction on the GVP path; the drift of the
 probability-flow ODE is then the model output itself and the interval is [0, 1], /root/reference/transport/transport.py:85-112,
-209-218): ``Sampler(create_transport("GVP", "velocity", ...)).sample_ode(...)`` with the reference's call signature."""
+209-218): ``Sampler(create_transport("GVP", "velocity", ...)).sample_ode(...)`` with the reference's call signature.
+
+``Sampler.sample_sde`` is the reference's second sampler entry (transport/transport.py:322-382, the stepper class ``sde`` of
+transport/integrators.py:8-75) for a velocity model on the GVP / Linear path: device-resident for a HIP denoiser
+(``sample_sde_device``, csrc/ode_sde.hip), an eager torch loop with the same formulas for any other callable."""
 from __future__ import annotations
 
+import math
 import os
 
+import numpy as np
 import torch
 
 from .odeint import odeint
@@ -50,13 +56,19 @@ def integrate(model, x, t_grid, method, atol, rtol, model_kwargs, stats, drift=N
 
 
 class VelocityTransport:
-    """velocity prediction on a GVP / linear path: nothing to convert, the ODE runs over [0, 1]"""
+    """velocity prediction on a GVP / linear path: nothing to convert, the ODE runs over [0, 1]; the SDE over
+    [0, 1 - last_step_size] (/root/reference/transport/transport.py:85-112 with sample_eps = 0 and any diffusion form but "SBDM")"""
     train_eps = 0
     sample_eps = 0
 
+    def __init__(self, path_type="Linear"):
+        self.path_type = path_type
+
     def check_interval(self, *_, **kw):
         if kw.get("sde"):
-            raise NotImplementedError("SDE sampling: use the reference's transport package (INTEGRATION.md section 3)")
+            if kw.get("reverse"):
+                raise NotImplementedError("reverse-time integration: use the reference's transport package")
+            return (0, 1 - kw.get("last_step_size", 0.0))
         return (1, 0) if kw.get("reverse") else (0, 1)
 
 
@@ -64,13 +76,14 @@ def create_transport(path_type="Linear", prediction="velocity", loss_weight=None
     if prediction not in ("velocity", None) or path_type not in ("GVP", "Linear"):
         raise NotImplementedError(f"{prediction} prediction on the {path_type} path is served by the reference's own transport "
                                   "package with bind_reference_transport (INTEGRATION.md section 3)")
-    return VelocityTransport()
+    return VelocityTransport(path_type)
 
 
 class Sampler:
     def __init__(self, transport, guider_config=None):
         self.transport = transport
         self.last_ode = None
+        self.last_sde = None
 
     def sample_ode(self, *, sampling_method="dopri5", num_steps=50, atol=1e-6, rtol=1e-3, reverse=False, cfg=False):
         """-> ``fn(x, model, **model_kwargs) -> Tensor[num_steps, *x.shape]`` (the caller takes ``[-1]``)"""
@@ -80,6 +93,216 @@ class Sampler:
         run = _Run(torch.linspace(t0, t1, num_steps), sampling_method, atol, rtol)
         self.last_ode = run
         return run.sample
+
+
+    def sample_sde(self, *, sampling_method="Euler", diffusion_form="sigma", diffusion_norm=1.0, last_step="Mean", last_step_size=0.04,
+                   num_steps=250, seed=0, noise=None):
+        """-> ``fn(x, model, **model_kwargs) -> Tensor[num_steps, *x.shape]``: the reference's ``Sampler.sample_sde``
+        (/root/reference/transport/transport.py:322-382) for a velocity model, its keywords in its order.  Slot k is the state after
+        step k, the last slot the output of the last step -- the reference's list, stacked.
+
+        ``diffusion_form`` defaults to ``"sigma"``, SiT's command-line default, NOT to the reference signature's ``"SBDM"``: for a
+        velocity model ``"SBDM"`` starts at t0 = sample_eps = 0, where alpha'/alpha is infinite, and is NaN in the reference too --
+        it raises ``ValueError`` here.  ``"constant"`` (w = diffusion_norm) is served as the reference intends it (there it fails
+        with a TypeError in the stepper: ``th.sqrt`` of a Python float).  Heun with ``last_step=None`` on the Linear path evaluates
+        its second stage at t = 1, where the score divides by 1 - t = 0: ``ValueError``.
+
+        ``seed``: the noise of step k is Philox4x32-10 keyed by the seed (include/ga_dit.h), drawn inside the step kernel for a HIP
+        denoiser and restated on the host for any other callable; ``noise`` [num_steps - 1, n_draw ...]: normals to use instead.
+        For ``forward_with_cfg`` the two halves of the doubled state take the SAME noise (n_draw = half the state), so they stay
+        equal -- the reference draws them independently although both are evaluated as they are."""
+        if sampling_method not in ("Euler", "Heun"):
+            raise ValueError(f"unknown SDE sampling method {sampling_method!r} (have 'Euler', 'Heun')")
+        if diffusion_form == "SBDM":
+            raise ValueError('diffusion_form="SBDM" is non-finite at t0 = 0 for a velocity model (alpha\'/alpha is infinite there), in the '
+                             'reference as well: use "sigma", "linear", "constant", "decreasing" or "inccreasing-decreasing"')
+        if diffusion_form not in SDE_FORMS:
+            raise ValueError(f"unknown diffusion form {diffusion_form!r} (have {SDE_FORMS})")
+        if last_step not in ("Mean", "Tweedie", "Euler", None):
+            raise ValueError(f"unknown last step {last_step!r} (have 'Mean', 'Tweedie', 'Euler', None)")
+        if num_steps < 2:
+            raise ValueError("SDE sampling needs at least two grid points")
+        if last_step is None:
+            last_step_size = 0.0
+        path_type = getattr(self.transport, "path_type", "Linear")
+        if sampling_method == "Heun" and last_step is None and path_type == "Linear":
+            raise ValueError("Heun with last_step=None on the Linear path evaluates its second stage at t = 1, where the score "
+                             "divides by 1 - t = 0 (non-finite in the reference as well)")
+        t0, t1 = self.transport.check_interval(0, 0, diffusion_form=diffusion_form, sde=True, eval=True, reverse=False,
+                                               last_step_size=last_step_size)
+        coef = sde_coefficients(path_type, diffusion_form, diffusion_norm, torch.linspace(t0, t1, num_steps), last_step_size)
+        run = _SdeRun(coef, sampling_method, last_step, seed, noise)
+        self.last_sde = run
+        return run.sample
+
+
+SDE_FORMS = ("constant", "sigma", "linear", "decreasing", "inccreasing-decreasing")
+# columns of a coefficient row: include/ga_dit.h, GA_SDE_C_*
+C_T, C_DT, C_SQRT_DT, C_W, C_G, C_R, C_VAR, C_T2, C_W2, C_R2, C_VAR2, C_HALF_DT, C_ALPHA, C_SIG2A = range(14)
+COEF_STRIDE = 16
+SDE_STREAM = {"Euler": 0, "Heun": 1}    # Philox stream id = the phase that draws (GA_SDE_EM, GA_SDE_HEUN_PERTURB)
+
+
+def _path_terms(path_type, t):
+    """alpha, alpha', sigma, sigma' at the fp32 times ``t`` -- /root/reference/transport/path.py:23-29 (Linear) and :174-188 (GVP),
+    term by term; then r = alpha / alpha' and var = sigma^2 - r sigma' sigma of ``get_score_from_velocity`` (:70-84)"""
+    if path_type == "GVP":
+        alpha, d_alpha = torch.sin(t * np.pi / 2), np.pi / 2 * torch.cos(t * np.pi / 2)
+        sigma, d_sigma = torch.cos(t * np.pi / 2), -np.pi / 2 * torch.sin(t * np.pi / 2)
+    else:
+        alpha, d_alpha, sigma, d_sigma = t, 1, 1 - t, -1
+    r = alpha / d_alpha
+    var = sigma ** 2 - r * d_sigma * sigma
+    return alpha, sigma, r, var
+
+
+def _diffusion(form, norm, t, sigma):
+    """w(t) of ``compute_diffusion`` (path.py:45-68)"""
+    if form == "constant":
+        return torch.full_like(t, norm)
+    if form == "sigma":
+        return norm * sigma
+    if form == "linear":
+        return norm * (1 - t)
+    if form == "decreasing":
+        return 0.25 * (norm * torch.cos(np.pi * t) + 1) ** 2
+    return norm * torch.sin(np.pi * t) ** 2      # "inccreasing-decreasing" (sic)
+
+
+def sde_coefficients(path_type, form, norm, t, last_step_size):
+    """Everything of a step that depends on the time alone, once, in torch fp32 on the host: [len(t), COEF_STRIDE] -- one row per
+    interval (GaSdeStep.coef in include/ga_dit.h) and the last-step row at t[-1].  ``dt = t[1] - t[0]`` in fp32 as the reference's
+    stepper has it (integrators.py:23-24)."""
+    t = t.float()
+    ni = len(t) - 1
+    dt = t[1] - t[0]
+    coef = torch.zeros((ni + 1, COEF_STRIDE), dtype=torch.float32)
+    alpha, sigma, r, var = _path_terms(path_type, t)
+    w = _diffusion(form, norm, t, sigma)
+    coef[:, C_T], coef[:, C_W], coef[:, C_R], coef[:, C_VAR] = t, w, r, var
+    coef[:, C_G] = torch.sqrt(2 * w)
+    coef[:ni, C_DT], coef[:ni, C_SQRT_DT], coef[:ni, C_HALF_DT] = dt, torch.sqrt(dt), 0.5 * dt
+    t2 = t[:ni] + dt
+    _, sigma2, r2, var2 = _path_terms(path_type, t2)
+    coef[:ni, C_T2], coef[:ni, C_W2], coef[:ni, C_R2], coef[:ni, C_VAR2] = t2, _diffusion(form, norm, t2, sigma2), r2, var2
+    coef[ni, C_DT] = last_step_size
+    coef[ni, C_ALPHA], coef[ni, C_SIG2A] = alpha[ni], sigma[ni] ** 2 / alpha[ni]
+    return coef
+
+
+_M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+
+
+def philox_normals(seed, step, stream, n):
+    """The normals the step kernel draws (csrc/ode_sde.hip; the transform is written out in include/ga_dit.h), restated on the host:
+    Philox4x32-10 keyed by the 64-bit seed at the counters (j / 4, step, stream, 0), two Box-Muller pairs per block in fp32
+    -> float32 [n].  The integers are the kernel's; the normals agree with it to the accuracy of log / sin / cos."""
+    nb = (n + 3) // 4
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    mask = np.uint64(0xFFFFFFFF)
+    c0 = np.arange(nb, dtype=np.uint64)
+    c1 = np.full(nb, int(step) & 0xFFFFFFFF, dtype=np.uint64)
+    c2 = np.full(nb, int(stream) & 0xFFFFFFFF, dtype=np.uint64)
+    c3 = np.zeros(nb, dtype=np.uint64)
+    for _ in range(10):
+        p0, p1 = np.uint64(_M0) * c0, np.uint64(_M1) * c2
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & mask, (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & mask
+        k0, k1 = (k0 + _W0) & 0xFFFFFFFF, (k1 + _W1) & 0xFFFFFFFF
+    scale = np.float32(2.0 ** -24)
+    u1 = ((np.stack([c0, c2], 1) >> np.uint64(8)) + np.uint64(1)).astype(np.float32) * scale
+    u2 = (np.stack([c1, c3], 1) >> np.uint64(8)).astype(np.float32) * scale
+    radius = np.sqrt(np.float32(-2.0) * np.log(u1))
+    theta = np.float32(2.0 * math.pi) * u2
+    return np.stack([radius * np.cos(theta), radius * np.sin(theta)], 2).astype(np.float32).reshape(-1)[:n]
+
+
+def _sde_drift(row, v, x, late=False):
+    """drift = v + w * score, score = (r v - x) / var -- every operation rounded on its own, as the step kernel"""
+    w, r, var = (row[C_W2], row[C_R2], row[C_VAR2]) if late else (row[C_W], row[C_R], row[C_VAR])
+    score = (r * v - x) / var
+    return v + w * score, score
+
+
+def _sde_eager(model, x, coef, method, last_step, normals, model_kwargs, stats):
+    """The loop of integrators.py:29-75 and the last step of transport.py:290-320 in torch, with ONE model call per evaluation
+    point; ``coef`` lives on the device of ``x`` (every operand a tensor there: no host scalar, whose division torch's HIP kernels
+    turn into a multiplication by the reciprocal)."""
+    B = x.size(0)
+    ni = coef.shape[0] - 1
+    x = x.float()
+    out, nfe = [], 0
+    for k in range(ni):
+        row = coef[k]
+        tv = torch.ones(B, device=x.device) * row[C_T]
+        dw = normals(k) * row[C_SQRT_DT]
+        if method == "Euler":
+            drift, _ = _sde_drift(row, model(x, tv, **model_kwargs).float(), x)
+            mean = x + drift * row[C_DT]
+            x = mean + row[C_G] * dw
+            nfe += 1
+        else:
+            xhat = x + row[C_G] * dw
+            k1, _ = _sde_drift(row, model(xhat, tv, **model_kwargs).float(), xhat)
+            xp = xhat + row[C_DT] * k1
+            k2, _ = _sde_drift(row, model(xp, torch.ones(B, device=x.device) * row[C_T2], **model_kwargs).float(), xp, late=True)
+            x = xhat + row[C_HALF_DT] * (k1 + k2)
+            nfe += 2
+        out.append(x)
+    row = coef[ni]
+    if last_step is not None:
+        v = model(x, torch.ones(B, device=x.device) * row[C_T], **model_kwargs).float()
+        nfe += 1
+        drift, score = _sde_drift(row, v, x)
+        if last_step == "Mean":
+            x = x + drift * row[C_DT]
+        elif last_step == "Tweedie":
+            x = x / row[C_ALPHA] + row[C_SIG2A] * score
+        else:
+            x = x + v * row[C_DT]
+    out.append(x)
+    stats.update(nfe=nfe, steps=ni + 1, sde=True)
+    return torch.stack(out)
+
+
+class _SdeRun:
+    def __init__(self, coef, method, last_step, seed, noise):
+        self.coef, self.method, self.last_step, self.seed, self.noise, self.last_stats = coef, method, last_step, seed, noise, {}
+
+    def sample(self, x, model, **model_kwargs):
+        self.last_stats = {}
+        owner, name = getattr(model, "__self__", None), getattr(model, "__name__", "")
+        ni = self.coef.shape[0] - 1
+        pairs = name == "forward_with_cfg"
+        if pairs and x.size(0) % 2:
+            raise ValueError("forward_with_cfg takes a doubled state: the conditional and the unconditional half")
+        nd = x.numel() // 2 if pairs else x.numel()
+        noise = self.noise
+        if noise is not None:
+            if noise.shape[0] != ni or noise.numel() != ni * nd:
+                raise ValueError(f"noise holds {ni} steps of {nd} normals" + (" (one half of the doubled CFG state)" if pairs else ""))
+            noise = noise.reshape(ni, nd)
+        # the same test as ``integrate``'s ``fusable``
+        fusable = (x.device.type == "cuda" and name in ("forward_with_cfg", "forward_cond") and "context" in model_kwargs
+                   and set(model_kwargs) <= {"context", "cfg_scale"} and os.environ.get("GA_ODE_GRAPH", "1") != "0"
+                   and getattr(owner, "out_channels", None) == getattr(owner, "in_channels", None)
+                   and hasattr(owner, "sample_sde_device"))
+        if fusable:
+            out = owner.sample_sde_device(x, self.coef, model_kwargs["context"], method=self.method, last_step=self.last_step,
+                                          cfg_scale=model_kwargs.get("cfg_scale", 1.0), cfg=pairs, seed=self.seed, noise=noise)
+            evals = ni * (1 if self.method == "Euler" else 2) + (self.last_step is not None)
+            self.last_stats.update(nfe=evals, steps=ni + 1, sde=True, graph=True, fused=True)
+            return out
+        shape = ((x.size(0) // 2,) if pairs else (x.size(0),)) + tuple(x.shape[1:])
+
+        def normals(k):
+            z = noise[k].to(device=x.device, dtype=torch.float32) if noise is not None else \
+                torch.from_numpy(philox_normals(self.seed, k, SDE_STREAM[self.method], nd)).to(x.device)
+            z = z.reshape(shape)
+            return torch.cat([z, z], 0) if pairs else z
+
+        with torch.no_grad():
+            return _sde_eager(model, x, self.coef.to(x.device), self.method, self.last_step, normals, model_kwargs, self.last_stats)
 
 
 class _Run:

@@ -380,7 +380,7 @@ typedef struct GaDitSamplerStep {
     const int32_t *counter;   /* device: index of the grid interval this step integrates                */
     float *velocity;          /* NULL: the Euler step above.  Otherwise ONLY the velocity of the evaluation -- the model output, or with
                                  cfg the guided combination u + s (c - u) in BOTH halves (forward_with_cfg's return value) -- is written
-                                 here, [B', L, Cout]; dt / state / traj / counter are not used (the stages of ga_ode_dopri5_*)           */
+                                 here, [B', L, Cout]; dt / state / traj / counter are not used (the stages of ga_ode_dopri5_*, the evaluations of ga_sde_step) */
 } GaDitSamplerStep;
 
 typedef struct GaDitForwardArgs {
@@ -481,6 +481,83 @@ typedef struct GaOdeDopri5 {
 
 int ga_ode_dopri5_stage(const GaOdeDopri5 *ode, int32_t stage, void *stream);
 int ga_ode_dopri5_finish(const GaOdeDopri5 *ode, void *stream);
+
+/* ---- device-resident SDE sampling: the reference's Sampler.sample_sde (/root/reference/transport/transport.py:322-382) with its stepper
+ * class `sde` (transport/integrators.py:8-75) for a VELOCITY model on the GVP / Linear path.  With v = the model output at (x, t),
+ *     score = (r v - x) / var,  drift = v + w score                                              (path.py:70-84, transport.py:282-284)
+ * where w(t) is the diffusion coefficient, r = alpha / alpha', var = sigma^2 - r sigma' sigma: one evaluation per point (the reference
+ * calls the model once for the drift and once more for the score).  One step is a fixed chain of launches,
+ *     Euler-Maruyama:  ga_dit_forward(x = state, step.velocity = velocity);  ga_sde_step(EM);  ga_sde_step(ADVANCE)
+ *     Heun:            ga_sde_step(HEUN_PERTURB);  ga_dit_forward(x = xhat, ...);  ga_sde_step(HEUN_PREDICT);
+ *                      ga_dit_forward(x = state, ...);  ga_sde_step(HEUN_CORRECT);  ga_sde_step(ADVANCE)
+ * that reads the step index, the coefficients and the seed from device memory: capture it into a hipGraph once and replay it
+ * num_intervals times -- every replay integrates the next interval with fresh noise.  Then one last step (LAST_*) behind an evaluation
+ * at (state, t1).  Phases, each one launch over the n floats, every product / quotient / sum rounded on its own in the order written
+ * (xi: the step's normals, see below; c = *counter clamped to [0, num_intervals); row = coef row c):
+ *     EM            score = (r v - x) / var; drift = v + w score; mean = x + drift dt; x = mean + g (xi sqrt_dt); traj[c] = x
+ *     HEUN_PERTURB  xhat = x + g (xi sqrt_dt)
+ *     HEUN_PREDICT  k1 = v + w ((r v - xhat) / var); x = xhat + dt k1; timesteps[0..batch) = t2            (v evaluated at (xhat, t))
+ *     HEUN_CORRECT  k2 = v + w2 ((r2 v - x) / var2); x = xhat + half_dt (k1 + k2); traj[c] = x             (v evaluated at (x, t2))
+ *     LAST_MEAN     traj[num_intervals] = x + (v + w ((r v - x) / var)) dt          (last row: dt = last_step_size, coefficients at t1)
+ *     LAST_TWEEDIE  traj[num_intervals] = x / alpha + sig2a ((r v - x) / var)
+ *     LAST_EULER    traj[num_intervals] = x + v dt
+ *     LAST_NONE     traj[num_intervals] = x                                        (the reference appends the same tensor twice)
+ *     ADVANCE       one thread: c' = min(*counter + 1, num_intervals); timesteps[0..batch) = coef[c'].t; *counter = c'
+ * Noise of ga_sde_step (EM and HEUN_PERTURB): Philox4x32-10, key = (seed low word, seed high word), counter =
+ * (j / 4, c, phase, 0) for draw index j; with the four output words o0..o3, lane = j % 4, p = lane / 2:
+ *     u1 = ((o[2p] >> 8) + 1) * 2^-24  in (0, 1],   u2 = (o[2p + 1] >> 8) * 2^-24  in [0, 1),   radius = sqrt(-2 ln u1),
+ *     theta = fp32(2 pi) u2,   xi = radius * (lane odd ? sin theta : cos theta)                 (fp32; |xi| <= sqrt(48 ln 2) = 5.77)
+ * n_draw = cfg_pairs ? n / 2 : n; with cfg_pairs elements i and i + n / 2 (the two halves of a doubled CFG state) take the SAME normal
+ * j = i mod n / 2, so the halves stay equal -- a deliberate departure from the reference, which draws them independently although
+ * forward_with_cfg then evaluates the two halves at different x.  The step index comes from *counter, never from a launch
+ * argument: a value baked into a captured graph would repeat the same noise on every replay. */
+#define GA_SDE_EM 0
+#define GA_SDE_HEUN_PERTURB 1
+#define GA_SDE_HEUN_PREDICT 2
+#define GA_SDE_HEUN_CORRECT 3
+#define GA_SDE_LAST_MEAN 4
+#define GA_SDE_LAST_TWEEDIE 5
+#define GA_SDE_LAST_EULER 6
+#define GA_SDE_LAST_NONE 7
+#define GA_SDE_ADVANCE 8
+/* columns of a coefficient row (GA_SDE_COEF_STRIDE floats): rows 0 .. num_intervals - 1 one per interval, row num_intervals the last step */
+#define GA_SDE_C_T 0         /* time of the interval's left end (last row: t1)                */
+#define GA_SDE_C_DT 1        /* step size (last row: last_step_size)                          */
+#define GA_SDE_C_SQRT_DT 2
+#define GA_SDE_C_W 3         /* diffusion coefficient w(t)                                    */
+#define GA_SDE_C_G 4         /* sqrt(2 w)                                                     */
+#define GA_SDE_C_R 5         /* alpha / alpha'                                                */
+#define GA_SDE_C_VAR 6       /* sigma^2 - r sigma' sigma                                      */
+#define GA_SDE_C_T2 7        /* Heun: t + dt (fp32 sum) and w, r, var there                   */
+#define GA_SDE_C_W2 8
+#define GA_SDE_C_R2 9
+#define GA_SDE_C_VAR2 10
+#define GA_SDE_C_HALF_DT 11  /* 0.5 dt                                                        */
+#define GA_SDE_C_ALPHA 12    /* last row, Tweedie: alpha(t1) and sigma(t1)^2 / alpha(t1)      */
+#define GA_SDE_C_SIG2A 13
+#define GA_SDE_COEF_STRIDE 16
+
+typedef struct GaSdeStep {
+    int64_t n;               /* floats of the state: B' * L * C (<= 2^31 - 1; even with cfg_pairs)   */
+    int32_t batch;           /* B': entries of `timesteps` (<= 64)                                   */
+    int32_t num_intervals;   /* grid intervals = num_steps - 1                                       */
+    int32_t cfg_pairs;       /* 1: the state is a doubled CFG batch, both halves take the same noise */
+    float *state;            /* [n] updated in place                                                 */
+    const float *velocity;   /* [n] output of the evaluation in front (GaDitSamplerStep.velocity)    */
+    float *k1;               /* [n] Heun: first drift                                                */
+    float *xhat;             /* [n] Heun: perturbed state, input of the first evaluation             */
+    float *traj;             /* [num_intervals + 1, n]: slot k = state after step k, last slot = last step */
+    int32_t *counter;        /* device: index of the interval this step integrates                   */
+    float *timesteps;        /* [B'] time of the next evaluation                                     */
+    const float *coef;       /* [num_intervals + 1, GA_SDE_COEF_STRIDE] device                       */
+    const uint64_t *seed;    /* device uint64[1] (not read when `noise` is given)                    */
+    const float *noise;      /* optional [num_intervals, n_draw]: read instead of drawing            */
+    float *noise_out;        /* optional [n_draw]: the normals this launch used                      */
+} GaSdeStep;
+
+/* host only, no HIP call: the error code ga_sde_step returns for (step, phase) before it launches anything, or 0 */
+int ga_sde_step_check(const GaSdeStep *step, int32_t phase);
+int ga_sde_step(const GaSdeStep *step, int32_t phase, void *stream);
 
 const char *ga_dit_version(void);
 
