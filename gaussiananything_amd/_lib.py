@@ -94,12 +94,35 @@ class GaNearestArgs(ctypes.Structure):
                 ("target_lengths", ctypes.c_void_p), ("out_dist2", ctypes.c_void_p), ("out_idx", ctypes.c_void_p)]
 
 
+class GaKnnArgs(ctypes.Structure):
+    """include/ga_pointcloud.h: GaKnnArgs"""
+    _fields_ = [("batch", ctypes.c_int32), ("num_query", ctypes.c_int32), ("num_target", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("query", ctypes.c_void_p), ("target", ctypes.c_void_p), ("query_lengths", ctypes.c_void_p),
+                ("target_lengths", ctypes.c_void_p), ("out_dist2", ctypes.c_void_p), ("out_idx", ctypes.c_void_p)]
+
+
+class GaKnnPlan(ctypes.Structure):
+    """include/ga_pointcloud.h: GaKnnPlan"""
+    _fields_ = [("k_slots", ctypes.c_int32), ("threads", ctypes.c_int32), ("tile", ctypes.c_int32), ("grid_x", ctypes.c_int32),
+                ("grid_y", ctypes.c_int32)]
+
+
+class GaKnnBackwardArgs(ctypes.Structure):
+    """include/ga_pointcloud.h: GaKnnBackwardArgs"""
+    _fields_ = [("batch", ctypes.c_int32), ("num_query", ctypes.c_int32), ("num_target", ctypes.c_int32), ("k", ctypes.c_int32),
+                ("query", ctypes.c_void_p), ("target", ctypes.c_void_p), ("query_lengths", ctypes.c_void_p),
+                ("target_lengths", ctypes.c_void_p), ("idx", ctypes.c_void_p), ("grad_dist2", ctypes.c_void_p),
+                ("grad_query", ctypes.c_void_p), ("grad_target", ctypes.c_void_p)]
+
+
 GA_FPS_VARIANT_REGISTER, GA_FPS_VARIANT_STREAMING = 0, 1
+GA_PC_KNN_MAX_K = 32
 
 EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspace_layout2", "ga_surfel_forward", "ga_surfel_postprocess",
            "ga_surfel_backward", "ga_surfel_backward_scratch_bytes",
            "ga_tsdf_integrate", "ga_tsdf_mesh_scratch_bytes", "ga_tsdf_mesh_count", "ga_tsdf_mesh_emit", "ga_mesh_write_obj", "ga_mesh_cluster_labels",
-           "ga_pc_fps", "ga_pc_fps_plan", "ga_pc_fps_workspace_bytes", "ga_pc_nearest")
+           "ga_pc_fps", "ga_pc_fps_plan", "ga_pc_fps_workspace_bytes", "ga_pc_nearest",
+           "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward")
 
 _lib = None
 
@@ -163,6 +186,12 @@ def lib():
         L.ga_pc_fps_workspace_bytes.argtypes = [ctypes.c_int32] * 3
         L.ga_pc_nearest.restype = ctypes.c_int
         L.ga_pc_nearest.argtypes = [ctypes.POINTER(GaNearestArgs), ctypes.c_void_p]
+        L.ga_pc_knn.restype = ctypes.c_int
+        L.ga_pc_knn.argtypes = [ctypes.POINTER(GaKnnArgs), ctypes.c_void_p]
+        L.ga_pc_knn_plan.restype = ctypes.c_int
+        L.ga_pc_knn_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GaKnnPlan)]
+        L.ga_pc_knn_backward.restype = ctypes.c_int
+        L.ga_pc_knn_backward.argtypes = [ctypes.POINTER(GaKnnBackwardArgs), ctypes.c_void_p]
         _lib = L
     return _lib
 

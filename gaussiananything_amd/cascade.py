@@ -159,15 +159,20 @@ def cascade(stage1, stage2, decoder, cond, uc, cameras=None, cfg_scale=4.0, seed
 
 
 @torch.no_grad()
-def cloud_to_condition(points, num_points, lengths=None):
+def cloud_to_condition(points, num_points, lengths=None, outlier_neighbors=None, outlier_std_ratio=2.0):
     """Any cloud [S,N,3] -- a scan, mesh samples, a stage-1 output with points added or removed -- as the ``fps-xyz`` stage 2 and the
     decoder are built for: ``num_points`` farthest points from index 0 when N > num_points (``pytorch3d.ops.sample_farthest_points``
     in the reference, whence the key's name; the HIP kernel of ``pointcloud`` here), the cloud itself in its own order when
     N == num_points, clipped to +-0.45 either way (flow_matching_trainer.py:1079).  ``lengths`` [S]: the valid points of each padded
-    cloud, every one at least ``num_points``."""
+    cloud, every one at least ``num_points``.  ``outlier_neighbors`` = k: ``pointcloud.remove_statistical_outliers(points, lengths,
+    k, outlier_std_ratio)`` runs first -- farthest point sampling picks stray points of a scan FIRST by construction -- and the
+    length requirement applies to what the filter leaves; None (default) runs no filter."""
     if points.dim() != 3 or points.shape[-1] != 3:
         raise ValueError("points is an [S, N, 3] cloud")
     N = points.shape[1]
+    if outlier_neighbors is not None and N >= num_points:
+        from .pointcloud import remove_statistical_outliers
+        points, lengths, _ = remove_statistical_outliers(points, lengths, outlier_neighbors, outlier_std_ratio)
     lens = [N] * points.shape[0] if lengths is None else [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
     if N < num_points or min(lens) < num_points:
         raise ValueError(f"a cloud of {min(N, min(lens))} points cannot condition a model of {num_points}: add points, the sampler only removes them")
@@ -180,18 +185,19 @@ def cloud_to_condition(points, num_points, lengths=None):
 @torch.no_grad()
 def from_point_cloud(stage2, decoder, cond, uc, points, cameras=None, cfg_scale=4.0, seed=42, num_steps=250,
                      sampling_method="dopri5", render_all_scale=True, stage2_zero_image_uc=False, stats=None, lengths=None,
-                     **ode_kwargs):
+                     outlier_neighbors=None, outlier_std_ratio=2.0, **ode_kwargs):
     """Stage 2 -> surfel decode (-> renders) on a cloud of the USER's: the reference's stage-2 entry, which reads the cloud from a PLY
     file (flow_matching_trainer.py:1079 text mode, :1110-1134 image mode, with its ``# ! edit`` lines stretching the cloud by hand) --
     the paper's 3D editing: keep the image or caption, change the shape.  ``points`` [S,N,3] with N >= the decoder's token count goes
-    through ``cloud_to_condition``; everything after is exactly what ``cascade`` does behind its stage 1, for both conditionings.
+    through ``cloud_to_condition`` (with its outlier filter when ``outlier_neighbors`` is given); everything after is exactly what
+    ``cascade`` does behind its stage 1, for both conditionings.
     ``stats`` receives {'stage2': ...}."""
     S = cond["caption_crossattn" if _is_caption(cond) else "img_crossattn"].shape[0]
     L = decoder.vit_decoder.pos_embed.shape[1]
     if points.shape[0] != S:
         raise ValueError(f"{points.shape[0]} clouds for {S} conditionings")
     dev = next(stage2.parameters()).device
-    fps_xyz = cloud_to_condition(points.to(dev), L, lengths)
+    fps_xyz = cloud_to_condition(points.to(dev), L, lengths, outlier_neighbors, outlier_std_ratio)
     st2 = {} if stats is not None else None
     ret = _stage2_and_decode(stage2, decoder, cond, uc, fps_xyz, cameras, cfg_scale, seed, num_steps, sampling_method,
                              render_all_scale, stage2_zero_image_uc, st2, ode_kwargs)

@@ -16,6 +16,14 @@
 //   and an index >= n, so they never win against a real point (distance >= 0).
 // Nearest: queries across lanes, targets staged in LDS in tiles of kNearestTile and read by broadcast (ds_read_b128 of a wave-uniform
 //   address: four targets' x, y or z per read); strict `<` while walking targets upwards keeps the lowest index at ties.
+// kNN: the same walk, with a sorted list of S = k_slots (distance, index) pairs per lane in registers (one kernel instance per S in
+//   1, 2, 4, 8, 16, 32).  A target enters the list through a fully unrolled compare / select chain (compile-time register indices only)
+//   that the wave runs only when `d < worst` holds for at least one of its lanes (a ballot: the branch is wave-uniform, the chain is
+//   predicated per lane).  The chain places d behind every entry with distance <= d; targets arrive in ascending index, so equal
+//   distances stay in index order and the k-th place keeps the lower index.
+// kNN backward: query side one lane per query, k' ascending.  Target side one lane per TARGET: the workgroup walks the cloud's (i, k')
+//   entries upwards in LDS tiles (index, 2 * grad, the query's coordinates) and a lane accumulates where the index is its own -- the
+//   ascending order is the contract's, and no atomics are needed.
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
@@ -246,6 +254,186 @@ __global__ __launch_bounds__(kNearestThreads) void nearest_kernel(const float *_
     }
 }
 
+constexpr int kKnnThreads = 256;
+constexpr int kKnnTile = 1024;
+constexpr int kKnnGradTile = 1024;   // (i, k') entries staged per tile of the target-side backward
+
+// (d, t) into the ascending list behind every entry with distance <= d; a lane with d >= ld[S - 1] changes nothing.  Walking downwards,
+// ld[s - 1] is still the old value when slot s is rewritten.  With ld[s - 1] <= ld[s] the new distance of slot s is the MEDIAN of
+// (d, ld[s - 1], ld[s]) -- ld[s - 1] when d is below it (shift), d when it lies between, ld[s] otherwise: one v_med3_f32, which selects
+// one of its operands and rounds nothing.  The index follows with one compare per slot (shared by two neighbouring slots) and two selects.
+template <int S>
+__device__ __forceinline__ void knn_insert(float (&ld)[S], int (&li)[S], float d, int t) {
+    bool here = d < ld[S - 1];
+#pragma unroll
+    for (int s = S - 1; s >= 1; --s) {
+        const bool shift = d < ld[s - 1];
+        const int keep = here ? t : li[s];
+        li[s] = shift ? li[s - 1] : keep;
+        ld[s] = __builtin_amdgcn_fmed3f(d, ld[s - 1], ld[s]);
+        here = shift;
+    }
+    li[0] = here ? t : li[0];
+    ld[0] = here ? d : ld[0];
+}
+
+template <int S>
+__device__ __forceinline__ void knn_offer(float (&ld)[S], int (&li)[S], float d, int t) {
+    if (__ballot(d < ld[S - 1]) != 0) knn_insert<S>(ld, li, d, t);   // wave-uniform branch around the per-lane predicated chain
+}
+
+template <int S>
+__global__ __launch_bounds__(kKnnThreads) void knn_kernel(const float *__restrict__ query, const float *__restrict__ target,
+                                                          const int32_t *__restrict__ qlen, const int32_t *__restrict__ tlen, int Nq,
+                                                          int Nt, int k, float *__restrict__ out_d, int32_t *__restrict__ out_i) {
+    __shared__ __attribute__((aligned(16))) float tx[kKnnTile], ty[kKnnTile], tz[kKnnTile];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int q = blockIdx.x * kKnnThreads + tid;
+    const int nq = clampi(qlen ? qlen[b] : Nq, 0, Nq), nt = clampi(tlen ? tlen[b] : Nt, 0, Nt);
+    const size_t o = ((size_t)b * Nq + (size_t)q) * (size_t)k;
+    if (blockIdx.x * kKnnThreads >= nq) {   // the whole block is padding (block-uniform: no barrier is skipped by a part of it)
+        if (q < Nq)
+            for (int s = 0; s < k; ++s) { out_d[o + s] = 0.f; out_i[o + s] = 0; }
+        return;
+    }
+    const float *qp = query + (size_t)b * Nq * 3, *tp = target + (size_t)b * Nt * 3;
+    const bool live = q < nq;
+    const float qx = live ? qp[3 * (size_t)q] : 0.f, qy = live ? qp[3 * (size_t)q + 1] : 0.f, qz = live ? qp[3 * (size_t)q + 2] : 0.f;
+    float ld[S];
+    int li[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+        ld[s] = live ? __builtin_inff() : -__builtin_inff();   // a dead lane never asks for the chain: no d is below -inf
+        li[s] = 0;
+    }
+    for (int t0 = 0; t0 < nt; t0 += kKnnTile) {
+        const int cnt = nt - t0 < kKnnTile ? nt - t0 : kKnnTile;
+        __syncthreads();   // the previous tile has been read by every wave
+        for (int j = tid; j < cnt; j += kKnnThreads) {
+            const size_t g = 3 * (size_t)(t0 + j);
+            tx[j] = tp[g]; ty[j] = tp[g + 1]; tz[j] = tp[g + 2];
+        }
+        __syncthreads();
+        int j = 0;
+        for (; j + 4 <= cnt; j += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) knn_offer<S>(ld, li, dist2(qx, qy, qz, tx[j + u], ty[j + u], tz[j + u]), t0 + j + u);
+        }
+        for (; j < cnt; ++j) knn_offer<S>(ld, li, dist2(qx, qy, qz, tx[j], ty[j], tz[j]), t0 + j);
+    }
+    if (q < Nq) {
+        const int m = live ? (k < nt ? k : nt) : 0;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            if (s < k) {
+                out_d[o + s] = s < m ? ld[s] : 0.f;
+                out_i[o + s] = s < m ? li[s] : 0;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kKnnThreads) void knn_grad_query_kernel(const float *__restrict__ query, const float *__restrict__ target,
+                                                                     const int32_t *__restrict__ qlen, const int32_t *__restrict__ tlen,
+                                                                     const int32_t *__restrict__ idx, const float *__restrict__ grad, int Nq,
+                                                                     int Nt, int k, float *__restrict__ gq) {
+    const int b = blockIdx.y, q = blockIdx.x * kKnnThreads + threadIdx.x;
+    if (q >= Nq) return;
+    const int nq = clampi(qlen ? qlen[b] : Nq, 0, Nq), nt = clampi(tlen ? tlen[b] : Nt, 0, Nt);
+    const int m = k < nt ? k : nt;
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    if (q < nq) {
+        const float *qp = query + ((size_t)b * Nq + (size_t)q) * 3, *tp = target + (size_t)b * Nt * 3;
+        const size_t o = ((size_t)b * Nq + (size_t)q) * (size_t)k;
+        const float qx = qp[0], qy = qp[1], qz = qp[2];
+        for (int s = 0; s < m; ++s) {
+            const int j = clampi(idx[o + s], 0, nt - 1);   // a valid pair's index is in range by contract; the clamp keeps a broken one inside the buffer
+            const float c = 2.f * grad[o + s];
+            ax = ax + c * (qx - tp[3 * (size_t)j]);
+            ay = ay + c * (qy - tp[3 * (size_t)j + 1]);
+            az = az + c * (qz - tp[3 * (size_t)j + 2]);
+        }
+    }
+    float *out = gq + ((size_t)b * Nq + (size_t)q) * 3;
+    out[0] = ax; out[1] = ay; out[2] = az;
+}
+
+__global__ __launch_bounds__(kKnnThreads) void knn_grad_target_kernel(const float *__restrict__ query, const float *__restrict__ target,
+                                                                      const int32_t *__restrict__ qlen, const int32_t *__restrict__ tlen,
+                                                                      const int32_t *__restrict__ idx, const float *__restrict__ grad, int Nq,
+                                                                      int Nt, int k, float *__restrict__ gt) {
+    __shared__ __attribute__((aligned(16))) int si[kKnnGradTile];
+    __shared__ float sc[kKnnGradTile], sx[kKnnGradTile], sy[kKnnGradTile], sz[kKnnGradTile];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int j = blockIdx.x * kKnnThreads + tid;
+    const int nq = clampi(qlen ? qlen[b] : Nq, 0, Nq), nt = clampi(tlen ? tlen[b] : Nt, 0, Nt);
+    float *out = gt + ((size_t)b * Nt + (size_t)j) * 3;
+    if (blockIdx.x * kKnnThreads >= nt) {   // the whole block is padding (block-uniform)
+        if (j < Nt) { out[0] = 0.f; out[1] = 0.f; out[2] = 0.f; }
+        return;
+    }
+    const int m = k < nt ? k : nt;
+    const float *qp = query + (size_t)b * Nq * 3, *tp = target + (size_t)b * Nt * 3;
+    const int32_t *ip = idx + (size_t)b * Nq * (size_t)k;
+    const float *gp = grad + (size_t)b * Nq * (size_t)k;
+    const bool live = j < nt;
+    const int mine = live ? j : -2;   // staged indices are >= -1: a dead lane matches nothing
+    const float px = live ? tp[3 * (size_t)j] : 0.f, py = live ? tp[3 * (size_t)j + 1] : 0.f, pz = live ? tp[3 * (size_t)j + 2] : 0.f;
+    float ax = 0.f, ay = 0.f, az = 0.f;
+    const int total = nq * k;   // <= Nq * k < 2^31
+    for (int e0 = 0; e0 < total; e0 += kKnnGradTile) {
+        const int cnt = total - e0 < kKnnGradTile ? total - e0 : kKnnGradTile;
+        const int cnt4 = (cnt + 3) & ~3;
+        __syncthreads();   // the previous tile has been read by every wave
+        for (int l = tid; l < cnt4; l += kKnnThreads) {
+            const int e = e0 + l;
+            const int i = e / k, s = e - i * k;
+            const bool valid = l < cnt && s < m;   // validity from the lengths; the index of an invalid pair is not even read
+            si[l] = valid ? ip[e] : -1;
+            sc[l] = valid ? 2.f * gp[e] : 0.f;
+            sx[l] = valid ? qp[3 * (size_t)i] : 0.f;
+            sy[l] = valid ? qp[3 * (size_t)i + 1] : 0.f;
+            sz[l] = valid ? qp[3 * (size_t)i + 2] : 0.f;
+        }
+        __syncthreads();
+        for (int l = 0; l < cnt4; l += 4) {
+            const int i0 = si[l], i1 = si[l + 1], i2 = si[l + 2], i3 = si[l + 3];
+            if (__ballot(i0 == mine || i1 == mine || i2 == mine || i3 == mine) == 0) continue;   // wave-uniform
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if ((u == 0 ? i0 : u == 1 ? i1 : u == 2 ? i2 : i3) == mine) {
+                    const float c = sc[l + u];
+                    ax = ax + (-(c * (sx[l + u] - px)));
+                    ay = ay + (-(c * (sy[l + u] - py)));
+                    az = az + (-(c * (sz[l + u] - pz)));
+                }
+            }
+        }
+    }
+    if (j < Nt) { out[0] = ax; out[1] = ay; out[2] = az; }
+}
+
+bool knn_shape_ok(int64_t B, int64_t Nq, int64_t Nt, int64_t k, int64_t kmax) {
+    const int64_t lim = int64_t(1) << 31;
+    return B > 0 && B <= GA_PC_MAX_BATCH && Nq > 0 && Nt > 0 && k >= 1 && k <= kmax && Nq * 3 < lim && Nt * 3 < lim && Nq * k < lim;
+}
+
+void knn_plan(int Nq, int k, GaKnnPlan &pl) {
+    int S = 1;
+    while (S < k) S *= 2;
+    pl.k_slots = S;
+    pl.threads = kKnnThreads;
+    pl.tile = kKnnTile;
+    pl.grid_x = (Nq + kKnnThreads - 1) / kKnnThreads;
+    pl.grid_y = 1;
+}
+
+template <int S>
+void launch_knn(const GaKnnArgs &a, const GaKnnPlan &pl, hipStream_t s) {
+    hipLaunchKernelGGL((knn_kernel<S>), dim3(pl.grid_x, pl.grid_y * a.batch), dim3(pl.threads), 0, s, a.query, a.target, a.query_lengths,
+                       a.target_lengths, a.num_query, a.num_target, a.k, a.out_dist2, a.out_idx);
+}
+
 bool fps_shape_ok(int64_t B, int64_t N, int64_t K) {
     return B > 0 && B <= GA_PC_MAX_BATCH && N > 0 && K > 0 && N * 3 < (int64_t(1) << 31);
 }
@@ -331,5 +519,54 @@ extern "C" int ga_pc_nearest(const GaNearestArgs *args, void *stream_v) {
     const unsigned blocks = (unsigned)((a.num_query + kNearestThreads - 1) / kNearestThreads);
     hipLaunchKernelGGL(nearest_kernel, dim3(blocks, a.batch), dim3(kNearestThreads), 0, s, a.query, a.target, a.query_lengths,
                        a.target_lengths, a.num_query, a.num_target, a.out_dist2, a.out_idx);
+    return hipGetLastError() == hipSuccess ? GA_OK : GA_ERR_LAUNCH;
+}
+
+extern "C" int ga_pc_knn_plan(int32_t num_query, int32_t num_target, int32_t k, GaKnnPlan *plan) {
+    if (!plan) return GA_ERR_NULL_ARG;
+    if (!knn_shape_ok(1, num_query, num_target, k, GA_PC_KNN_MAX_K)) return GA_ERR_BAD_SHAPE;
+    knn_plan(num_query, k, *plan);
+    return GA_OK;
+}
+
+extern "C" int ga_pc_knn(const GaKnnArgs *args, void *stream_v) {
+    if (!args) return GA_ERR_NULL_ARG;
+    const GaKnnArgs &a = *args;
+    if (!knn_shape_ok(a.batch, a.num_query, a.num_target, a.k, GA_PC_KNN_MAX_K)) return GA_ERR_BAD_SHAPE;
+    if (!a.query || !a.target || !a.out_dist2 || !a.out_idx) return GA_ERR_NULL_ARG;
+    GaKnnPlan pl;
+    knn_plan(a.num_query, a.k, pl);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream_v);
+    (void)hipGetLastError();
+    switch (pl.k_slots) {
+        case 1: launch_knn<1>(a, pl, s); break;
+        case 2: launch_knn<2>(a, pl, s); break;
+        case 4: launch_knn<4>(a, pl, s); break;
+        case 8: launch_knn<8>(a, pl, s); break;
+        case 16: launch_knn<16>(a, pl, s); break;
+        case 32: launch_knn<32>(a, pl, s); break;
+        default: return GA_ERR_BAD_SHAPE;   // unreachable: knn_plan yields only the instances above
+    }
+    return hipGetLastError() == hipSuccess ? GA_OK : GA_ERR_LAUNCH;
+}
+
+extern "C" int ga_pc_knn_backward(const GaKnnBackwardArgs *args, void *stream_v) {
+    if (!args) return GA_ERR_NULL_ARG;
+    const GaKnnBackwardArgs &a = *args;
+    if (!knn_shape_ok(a.batch, a.num_query, a.num_target, a.k, INT32_MAX)) return GA_ERR_BAD_SHAPE;
+    if (!a.query || !a.target || !a.idx || !a.grad_dist2) return GA_ERR_NULL_ARG;
+    if (!a.grad_query && !a.grad_target) return GA_OK;   // nothing asked for
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream_v);
+    (void)hipGetLastError();
+    if (a.grad_query) {
+        const unsigned blocks = (unsigned)((a.num_query + kKnnThreads - 1) / kKnnThreads);
+        hipLaunchKernelGGL(knn_grad_query_kernel, dim3(blocks, a.batch), dim3(kKnnThreads), 0, s, a.query, a.target, a.query_lengths,
+                           a.target_lengths, a.idx, a.grad_dist2, a.num_query, a.num_target, a.k, a.grad_query);
+    }
+    if (a.grad_target) {
+        const unsigned blocks = (unsigned)((a.num_target + kKnnThreads - 1) / kKnnThreads);
+        hipLaunchKernelGGL(knn_grad_target_kernel, dim3(blocks, a.batch), dim3(kKnnThreads), 0, s, a.query, a.target, a.query_lengths,
+                           a.target_lengths, a.idx, a.grad_dist2, a.num_query, a.num_target, a.k, a.grad_target);
+    }
     return hipGetLastError() == hipSuccess ? GA_OK : GA_ERR_LAUNCH;
 }

@@ -4,14 +4,19 @@
                              (/root/reference/nsr/lsgm/flow_matching_trainer.py:1079, :1110-1134) and generated surfels into the
                              ``fps-4096.ply`` the geometry metrics are computed on (/root/reference/scripts/save_pcd_from_gs.py:148-185)
     nearest_points           nearest target (squared distance, index) of every query
-    chamfer_distance         pytorch3d.loss.chamfer_distance for squared L2 without normals (/root/reference/nsr/train_nv_util.py:2244),
-                             forward only
+    chamfer_distance         pytorch3d.loss.chamfer_distance for squared L2 without normals (/root/reference/nsr/train_nv_util.py:2244);
+                             forward only by default, with gradients for ``differentiable=True`` (the reference's use as a loss)
+    knn_points, knn_gather   pytorch3d.ops.knn_points / knn_gather (nsr/srt/encoder.py:884-923 of the reference), K <= 32, squared L2,
+                             with gradients through ``ga_pc_knn_backward``
+    remove_statistical_outliers   mean distance to the k nearest neighbours against the cloud's mean + ratio * deviation: OUR OWN
+                             definition, parity with Open3D's filter of the same name is not claimed
 
 pytorch3d is absent from this image; its published behaviour is restated, parity UNPINNED ('Point clouds').  The tensors
 stay on the device and the work goes on the current stream.  There is no CPU fallback: without the HIP library, or on a CPU tensor,
 the calls raise."""
 from __future__ import annotations
 
+import collections
 import ctypes
 import random
 from typing import Optional
@@ -106,29 +111,203 @@ def nearest_points(x: torch.Tensor, y: torch.Tensor, x_lengths=None, y_lengths=N
     return dist2, idx.long()
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _knn_backward(q, t, ql, tl, idx, grad, want_query, want_target):
+    """``ga_pc_knn_backward`` on fp32 contiguous clouds, int32 ``idx`` [B,Nq,K] and fp32 ``grad`` [B,Nq,K] -> (grad_query, grad_target),
+    each None when not wanted"""
+    B, Nq, _ = q.shape
+    Nt = t.shape[1]
+    K = idx.shape[2]
+    gq = torch.empty_like(q) if want_query else None
+    gt = torch.empty_like(t) if want_target else None
+    args = _lib.GaKnnBackwardArgs(B, Nq, Nt, K, q.data_ptr(), t.data_ptr(), _ptr(ql), _ptr(tl), idx.data_ptr(), grad.data_ptr(),
+                                  _ptr(gq), _ptr(gt))
+    with torch.cuda.device(q.device):
+        _lib.check(_lib.lib().ga_pc_knn_backward(ctypes.byref(args), _stream(q.device)), "ga_pc_knn_backward")
+    return gq, gt
+
+
+class _NearestDist2(torch.autograd.Function):
+    """squared distance of every point of ``x`` to its nearest point of ``y``: forward ``ga_pc_nearest``, backward
+    ``ga_pc_knn_backward`` with k = 1 on the saved indices (the -1 of padded slots is never dereferenced: validity is the lengths')"""
+
+    @staticmethod
+    def forward(ctx, x, y, xl, yl):
+        xs, ys = _cloud(x, "x"), _cloud(y, "y")
+        B, Nx, _ = xs.shape
+        dist2 = torch.empty(B, Nx, dtype=torch.float32, device=xs.device)
+        idx = torch.empty(B, Nx, dtype=torch.int32, device=xs.device)
+        args = _lib.GaNearestArgs(B, Nx, ys.shape[1], xs.data_ptr(), ys.data_ptr(), _ptr(xl), _ptr(yl), dist2.data_ptr(), idx.data_ptr())
+        with torch.cuda.device(xs.device):
+            _lib.check(_lib.lib().ga_pc_nearest(ctypes.byref(args), _stream(xs.device)), "ga_pc_nearest")
+        ctx.save_for_backward(xs, ys, idx)
+        ctx.lengths = (xl, yl)
+        ctx.dtypes = (x.dtype, y.dtype)
+        return dist2
+
+    @staticmethod
+    def backward(ctx, grad):
+        xs, ys, idx = ctx.saved_tensors
+        gx, gy = _knn_backward(xs, ys, ctx.lengths[0], ctx.lengths[1], idx.unsqueeze(-1), grad.to(torch.float32).contiguous().unsqueeze(-1),
+                               ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return (gx.to(ctx.dtypes[0]) if gx is not None else None, gy.to(ctx.dtypes[1]) if gy is not None else None, None, None)
+
+
 def chamfer_distance(x: torch.Tensor, y: torch.Tensor, x_lengths=None, y_lengths=None, batch_reduction: Optional[str] = "mean",
-                     point_reduction: str = "mean"):
+                     point_reduction: str = "mean", single_directional: bool = False, differentiable: bool = False):
     """-> (loss, None): ``pytorch3d.loss.chamfer_distance`` for squared L2 without normals -- for each direction the squared distance
     of every point to its nearest neighbour in the other cloud, summed (``point_reduction='sum'``) or averaged over the cloud's
     length ('mean'), the two directions added, then summed / averaged over the batch (``batch_reduction`` 'sum' | 'mean' | None =
-    one value per cloud).  Two ``ga_pc_nearest`` launches and torch reductions on the device.  Forward only."""
+    one value per cloud).  Two ``ga_pc_nearest`` launches and torch reductions on the device.  ``single_directional`` (pytorch3d's
+    keyword) drops the y -> x term.  Forward only unless ``differentiable``: then the per-point distances come from an autograd
+    function whose backward is ``ga_pc_knn_backward`` (k = 1), the same reductions carry the weights, and the loss has the bits of
+    the forward-only one."""
     if point_reduction not in ("mean", "sum"):
         raise ValueError('point_reduction must be one of ["mean", "sum"]')
     if batch_reduction not in ("mean", "sum", None):
         raise ValueError('batch_reduction must be one of ["mean", "sum"] or None')
-    if (isinstance(x, torch.Tensor) and x.requires_grad) or (isinstance(y, torch.Tensor) and y.requires_grad):
-        raise RuntimeError("chamfer_distance is forward only: an input requires grad")
-    cham_x, _ = nearest_points(x, y, x_lengths, y_lengths)   # padded slots hold 0
-    cham_y, _ = nearest_points(y, x, y_lengths, x_lengths)
+    if differentiable:
+        xs, ys = _cloud(x, "x"), _cloud(y, "y")
+        if xs.shape[0] != ys.shape[0] or xs.device != ys.device:
+            raise ValueError("x and y need the same batch size and device")
+        xl, _ = _lengths(x_lengths, xs.shape[0], xs.shape[1], xs.device, "x_lengths")
+        yl, _ = _lengths(y_lengths, xs.shape[0], ys.shape[1], xs.device, "y_lengths")
+        cham_x = _NearestDist2.apply(x, y, xl, yl)
+        cham_y = None if single_directional else _NearestDist2.apply(y, x, yl, xl)
+    else:
+        if (isinstance(x, torch.Tensor) and x.requires_grad) or (isinstance(y, torch.Tensor) and y.requires_grad):
+            raise RuntimeError("chamfer_distance is forward only: an input requires grad")
+        cham_x, _ = nearest_points(x, y, x_lengths, y_lengths)   # padded slots hold 0
+        cham_y = None if single_directional else nearest_points(y, x, y_lengths, x_lengths)[0]
     B, Nx = cham_x.shape
-    Ny = cham_y.shape[1]
-    cham_x, cham_y = cham_x.sum(1), cham_y.sum(1)
-    if point_reduction == "mean":
-        xl = torch.as_tensor(x_lengths if x_lengths is not None else [Nx] * B, device=cham_x.device).to(torch.float32)
-        yl = torch.as_tensor(y_lengths if y_lengths is not None else [Ny] * B, device=cham_x.device).to(torch.float32)
-        cham_x, cham_y = cham_x / xl, cham_y / yl
-    if batch_reduction is not None:
-        cham_x, cham_y = cham_x.sum(), cham_y.sum()
-        if batch_reduction == "mean":
-            cham_x, cham_y = cham_x / B, cham_y / B
-    return cham_x + cham_y, None
+
+    def reduce(cham, lengths):
+        N = cham.shape[1]
+        cham = cham.sum(1)
+        if point_reduction == "mean":
+            cham = cham / torch.as_tensor(lengths if lengths is not None else [N] * B, device=cham.device).to(torch.float32)
+        if batch_reduction is not None:
+            cham = cham.sum()
+            if batch_reduction == "mean":
+                cham = cham / B
+        return cham
+
+    cham_x = reduce(cham_x, x_lengths)
+    if single_directional:
+        return cham_x, None
+    return cham_x + reduce(cham_y, y_lengths), None
+
+
+KNN = collections.namedtuple("KNN", "dists idx knn")
+
+
+def knn_plan(num_query: int, num_target: int, K: int = 1) -> dict:
+    """What ``ga_pc_knn`` launches: {'k_slots', 'threads', 'tile', 'grid_x', 'grid_y'} (the grid is grid_x by grid_y * B)."""
+    pl = _lib.GaKnnPlan()
+    _lib.check(_lib.lib().ga_pc_knn_plan(int(num_query), int(num_target), int(K), ctypes.byref(pl)), "ga_pc_knn_plan")
+    return {"k_slots": pl.k_slots, "threads": pl.threads, "tile": pl.tile, "grid_x": pl.grid_x, "grid_y": pl.grid_y}
+
+
+def _knn_forward(q, t, ql, tl, K):
+    B, Nq, _ = q.shape
+    dist2 = torch.empty(B, Nq, K, dtype=torch.float32, device=q.device)
+    idx = torch.empty(B, Nq, K, dtype=torch.int32, device=q.device)
+    args = _lib.GaKnnArgs(B, Nq, t.shape[1], K, q.data_ptr(), t.data_ptr(), _ptr(ql), _ptr(tl), dist2.data_ptr(), idx.data_ptr())
+    with torch.cuda.device(q.device):
+        _lib.check(_lib.lib().ga_pc_knn(ctypes.byref(args), _stream(q.device)), "ga_pc_knn")
+    return dist2, idx
+
+
+class _KnnDist2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p1, p2, l1, l2, K):
+        q, t = _cloud(p1, "p1"), _cloud(p2, "p2")
+        dist2, idx = _knn_forward(q, t, l1, l2, K)
+        ctx.save_for_backward(q, t, idx)
+        ctx.lengths = (l1, l2)
+        ctx.dtypes = (p1.dtype, p2.dtype)
+        idx64 = idx.long()
+        ctx.mark_non_differentiable(idx64)
+        return dist2, idx64
+
+    @staticmethod
+    def backward(ctx, grad, _grad_idx):
+        q, t, idx = ctx.saved_tensors
+        gq, gt = _knn_backward(q, t, ctx.lengths[0], ctx.lengths[1], idx, grad.to(torch.float32).contiguous(),
+                               ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return (gq.to(ctx.dtypes[0]) if gq is not None else None, gt.to(ctx.dtypes[1]) if gt is not None else None, None, None, None)
+
+
+def knn_points(p1: torch.Tensor, p2: torch.Tensor, lengths1=None, lengths2=None, norm: int = 2, K: int = 1, version: int = -1,
+               return_nn: bool = False, return_sorted: bool = True):
+    """-> KNN(dists [B,N1,K] float32 SQUARED, idx [B,N1,K] int64, knn [B,N1,K,3] or None): ``pytorch3d.ops.knn_points`` for the
+    squared L2 norm.  Lists are ascending, the lower index first among equal distances; slots past ``min(K, lengths2[b])`` and the
+    rows past ``lengths1[b]`` hold distance 0 and index 0, pytorch3d's zero padding.  ``version`` is accepted and ignored; the output
+    is always sorted, which also satisfies ``return_sorted=False``.  When ``p1`` or ``p2`` requires grad, ``dists`` carries the
+    gradient (``ga_pc_knn_backward``)."""
+    if norm == 1:
+        raise NotImplementedError("knn_points: the L1 norm is not built, only norm=2")
+    if norm != 2:
+        raise ValueError("knn_points supports norm=2 (squared L2) only")
+    K = int(K)
+    if K < 1 or K > _lib.GA_PC_KNN_MAX_K:
+        raise ValueError(f"K must lie in [1, {_lib.GA_PC_KNN_MAX_K}]: the sorted list lives in registers, {_lib.GA_PC_KNN_MAX_K} is the limit")
+    q, t = _cloud(p1, "p1"), _cloud(p2, "p2")
+    if q.shape[0] != t.shape[0] or q.device != t.device:
+        raise ValueError("p1 and p2 need the same batch size and device")
+    B, N1, _ = q.shape
+    l1, _ = _lengths(lengths1, B, N1, q.device, "lengths1")
+    l2, _ = _lengths(lengths2, B, t.shape[1], q.device, "lengths2")
+    if torch.is_grad_enabled() and (p1.requires_grad or p2.requires_grad):
+        dists, idx = _KnnDist2.apply(p1, p2, l1, l2, K)
+    else:
+        dists, idx = _knn_forward(q, t, l1, l2, K)
+        idx = idx.long()
+    return KNN(dists, idx, knn_gather(p2, idx, lengths2) if return_nn else None)
+
+
+def knn_gather(x: torch.Tensor, idx: torch.Tensor, lengths=None):
+    """``pytorch3d.ops.knn_gather``: x [B,M,C], idx [B,N,K] -> [B,N,K,C] with out[b,n,k] = x[b, idx[b,n,k]], zero where
+    ``k >= lengths[b]`` (``lengths`` [B]: the lengths of ``x``'s clouds).  Plain torch ``gather``, differentiable in ``x``."""
+    if x.dim() != 3 or idx.dim() != 3 or x.shape[0] != idx.shape[0]:
+        raise ValueError("x is [B, M, C] and idx [B, N, K] with the same B")
+    B, M, C = x.shape
+    _, N, K = idx.shape
+    out = x[:, :, None].expand(-1, -1, K, -1).gather(1, idx[:, :, :, None].expand(-1, -1, -1, C))
+    if lengths is not None:
+        ln = torch.as_tensor(lengths, device=x.device).to(torch.int64)
+        if ln.shape != (B,):
+            raise ValueError("lengths is a [B] tensor")
+        pad = ln[:, None] <= torch.arange(K, device=x.device)[None]          # [B,K]
+        out = out.masked_fill(pad[:, None, :, None], 0)
+    return out
+
+
+@torch.no_grad()
+def remove_statistical_outliers(points: torch.Tensor, lengths=None, nb_neighbors: int = 20, std_ratio: float = 2.0):
+    """-> (points [B,N,3], lengths [B] int64, keep_mask [B,N] bool).  Per valid point, m_i is the mean of sqrt(dist2) to its
+    ``nb_neighbors`` nearest OTHER points (``knn_points`` of the cloud against itself with K = nb_neighbors + 1, the first entry --
+    the point itself, or a duplicate of it at distance 0 -- dropped); per cloud, mu and sigma are the mean and the population
+    standard deviation of m; point i stays iff m_i <= mu + std_ratio * sigma.  Kept points move to the front in their original
+    order, zeros follow.  This is our own definition: parity with Open3D's ``remove_statistical_outlier`` is not claimed."""
+    p = _cloud(points, "points")
+    B, N, _ = p.shape
+    nb = int(nb_neighbors)
+    if nb < 1 or nb + 1 > _lib.GA_PC_KNN_MAX_K:
+        raise ValueError(f"nb_neighbors must lie in [1, {_lib.GA_PC_KNN_MAX_K - 1}]")
+    _, host = _lengths(lengths, B, N, p.device, "lengths")
+    if min(host) < nb + 1:
+        raise ValueError(f"a cloud of {min(host)} points has no {nb} neighbours per point")
+    m = knn_points(p, p, host, host, K=nb + 1).dists[:, :, 1:].sqrt().mean(-1)                        # [B,N]
+    ln = torch.tensor(host, dtype=torch.int64, device=p.device)
+    valid = torch.arange(N, device=p.device)[None] < ln[:, None]
+    cnt = ln.to(torch.float32)
+    mu = (m * valid).sum(1) / cnt
+    sigma = (((m - mu[:, None]).square() * valid).sum(1) / cnt).sqrt()
+    keep = valid & (m <= (mu + float(std_ratio) * sigma)[:, None])
+    order = torch.argsort((~keep).to(torch.uint8), dim=1, stable=True)                               # kept first, original order
+    out = p.gather(1, order[:, :, None].expand(-1, -1, 3)) * keep.gather(1, order)[:, :, None]
+    return out, keep.sum(1), keep

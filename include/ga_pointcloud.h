@@ -1,11 +1,13 @@
 /*
- * ga_pointcloud.h -- C-ABI of the MI355X-native point-cloud operations on the generation side: farthest point sampling and
- * nearest point (the building block of the Chamfer distance).
+ * ga_pointcloud.h -- C-ABI of the MI355X-native point-cloud operations on the generation side: farthest point sampling,
+ * nearest point (the building block of the Chamfer distance), the k nearest neighbours and the gradient of their squared distances.
  *
  * Replaces, for a cloud the USER hands to stage 2 and for the evaluation hand-off of generated surfels,
  *     pytorch3d.ops.sample_farthest_points      (fps-xyz of the stage-2 entry, /root/reference/nsr/lsgm/flow_matching_trainer.py:1079, :1110-1134;
  *                                                fps-4096.ply of /root/reference/scripts/save_pcd_from_gs.py:148-185)
- *     pytorch3d.loss.chamfer_distance           (/root/reference/nsr/train_nv_util.py:2244; squared L2, no normals: two nearest-point passes)
+ *     pytorch3d.loss.chamfer_distance           (/root/reference/nsr/train_nv_util.py:2244; squared L2, no normals: two nearest-point passes;
+ *                                                as a loss with gradients at :2244-2267: ga_pc_knn_backward with k = 1)
+ *     pytorch3d.ops.knn_points / knn_gather     (nsr/srt/encoder.py:884-923 of the reference; ga_pc_knn, k <= GA_PC_KNN_MAX_K)
  * pytorch3d is a third-party dependency that is absent from this image and does not build for ROCm; its published behaviour is
  * restated in tests/_pointcloud_ref.py, parity UNPINNED ('Point clouds').
  *
@@ -13,12 +15,17 @@
  * negative GA_ERR_* code is returned, no exceptions, no host synchronisation.  Every argument the host can see is validated before
  * anything touches the device.
  *
- * ARITHMETIC CONTRACT (both kernels).  Everything is fp32.  The squared distance of two points is
+ * ARITHMETIC CONTRACT (every kernel).  Everything is fp32.  The squared distance of two points is
  *     dx = ax - bx; dy = ay - by; dz = az - bz;   d = dx*dx;  d = d + dy*dy;  d = d + dz*dz;
  * with every operation rounded on its own (the translation unit is built with -ffp-contract=off): the results are a function of the
  * inputs alone, and a numpy float32 restatement reproduces them bit for bit.  Non-finite coordinates are the caller's error and are
  * not checked.  Lengths and start indices live on the device and cannot be validated by the host: the caller keeps
  * 1 <= lengths[b] <= N and 0 <= start_idx[b] < lengths[b]; the kernels clamp them into range so that no access leaves the buffers.
+ *
+ * PADDING.  ga_pc_fps and ga_pc_nearest mark an unused slot with index -1.  ga_pc_knn marks it with index 0 and distance 0, because
+ * pytorch3d.ops.knn_points allocates its outputs as zeros and writes valid slots only (restated from its published behaviour, not
+ * pinned).  Neither value can be told from the index alone in the second case: validity always comes from the lengths, and
+ * ga_pc_knn_backward never dereferences a padding index of either kind.
  */
 #ifndef GA_POINTCLOUD_H
 #define GA_POINTCLOUD_H
@@ -83,6 +90,65 @@ typedef struct GaNearestArgs {
 } GaNearestArgs;
 
 int ga_pc_nearest(const GaNearestArgs *args, void *stream);
+
+#define GA_PC_KNN_MAX_K 32
+
+/* The k nearest targets of every query, brute force (pytorch3d.ops.knn_points, squared L2, sorted).  For query q of cloud b, with
+ * m = min(k, target_lengths[b]): slots 0 .. m-1 hold the m smallest pairs (dist2, target index) in ascending lexicographic order --
+ * among equal distances the lower index comes first, and at the k-th place the lower index is the one that stays.  Slots k' >= m, and
+ * every slot of a query past query_lengths[b], hold distance 0 and index 0 (NOT the -1 of ga_pc_nearest: see PADDING above).  A NaN
+ * coordinate is the caller's error. */
+typedef struct GaKnnArgs {
+    int32_t batch;                 /* B, 1 .. GA_PC_MAX_BATCH                                   */
+    int32_t num_query;             /* Nq, Nq * 3 < 2^31 and (int64) Nq * k < 2^31               */
+    int32_t num_target;            /* Nt, Nt * 3 < 2^31                                         */
+    int32_t k;                     /* 1 .. GA_PC_KNN_MAX_K                                      */
+    const float *query;            /* [B,Nq,3]                                                  */
+    const float *target;           /* [B,Nt,3]                                                  */
+    const int32_t *query_lengths;  /* [B] or NULL (= all Nq), clamped by the kernel             */
+    const int32_t *target_lengths; /* [B] or NULL (= all Nt), clamped by the kernel             */
+    float *out_dist2;              /* [B,Nq,k]                                                  */
+    int32_t *out_idx;              /* [B,Nq,k]                                                  */
+} GaKnnArgs;
+
+/* what ga_pc_knn launches for one cloud pair: grid (grid_x, grid_y * B) workgroups of `threads` lanes, one lane per query, the sorted
+ * list in `k_slots` register pairs, the targets staged in LDS tiles of `tile` points */
+typedef struct GaKnnPlan {
+    int32_t k_slots; /* register list length of the kernel instance that serves k: the smallest of 1, 2, 4, 8, 16, 32 that is >= k */
+    int32_t threads; /* queries per workgroup                                                                                    */
+    int32_t tile;    /* targets staged per LDS tile                                                                              */
+    int32_t grid_x;  /* ceil(Nq / threads)                                                                                       */
+    int32_t grid_y;  /* workgroups per cloud along y (1): targets are not split over workgroups                                  */
+} GaKnnPlan;
+
+/* host only, no HIP call: GA_OK, GA_ERR_NULL_ARG or GA_ERR_BAD_SHAPE (the limits of GaKnnArgs) */
+int ga_pc_knn_plan(int32_t num_query, int32_t num_target, int32_t k, GaKnnPlan *plan);
+int ga_pc_knn(const GaKnnArgs *args, void *stream);
+
+/* Gradient of the squared distances of ga_pc_knn (any k >= 1) or ga_pc_nearest (k = 1) with respect to both clouds.  A pair (i, k') is
+ * VALID when i < query_lengths[b] and k' < min(k, target_lengths[b]); validity never comes from the index value, and the index of an
+ * invalid pair (0 or -1) is never dereferenced.  For a valid pair with j = idx[b,i,k']:
+ *     c = 2 * grad_dist2[b,i,k'];   u_a = c * (query[b,i,a] - target[b,j,a])          a = x, y, z, every operation rounded on its own
+ *     grad_query[b,i,a]  = +0, then + u_a   over k' ascending
+ *     grad_target[b,j,a] = +0, then + (-u_a) over all valid pairs with idx == j, in ascending (i, k') order
+ * Rows past the lengths, and targets nobody selected, get exactly 0.  The order is part of the contract: no floating-point atomics,
+ * the result is a function of the inputs alone.  A valid pair's index must lie in [0, target_lengths[b]). */
+typedef struct GaKnnBackwardArgs {
+    int32_t batch;                 /* B, 1 .. GA_PC_MAX_BATCH                                   */
+    int32_t num_query;             /* Nq, Nq * 3 < 2^31 and (int64) Nq * k < 2^31               */
+    int32_t num_target;            /* Nt, Nt * 3 < 2^31                                         */
+    int32_t k;                     /* >= 1                                                      */
+    const float *query;            /* [B,Nq,3]                                                  */
+    const float *target;           /* [B,Nt,3]                                                  */
+    const int32_t *query_lengths;  /* [B] or NULL                                               */
+    const int32_t *target_lengths; /* [B] or NULL                                               */
+    const int32_t *idx;            /* [B,Nq,k] as ga_pc_knn / ga_pc_nearest wrote it            */
+    const float *grad_dist2;       /* [B,Nq,k]                                                  */
+    float *grad_query;             /* [B,Nq,3] or NULL                                          */
+    float *grad_target;            /* [B,Nt,3] or NULL                                          */
+} GaKnnBackwardArgs;
+
+int ga_pc_knn_backward(const GaKnnBackwardArgs *args, void *stream);
 
 #ifdef __cplusplus
 }
