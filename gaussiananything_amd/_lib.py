@@ -20,7 +20,17 @@ GA_SURFEL_FLAG_STATS, GA_SURFEL_FLAG_WORKSPACE_CLEAN, GA_SURFEL_FLAG_SPLIT_WALK,
 GA_SEG_EPOCH_WORD = 96   # csrc/surfel_common.h: kSegEpochWord
 GA_SURFEL_RECORD_FLOATS = 24
 GA_SURFEL_STAGE_EVENTS = 5
-_ERR = {-1: "GA_ERR_NULL_ARG", -2: "GA_ERR_BAD_SHAPE", -3: "GA_ERR_WORKSPACE", -4: "GA_ERR_LAUNCH"}
+_ERR = {-1: "GA_ERR_NULL_ARG", -2: "GA_ERR_BAD_SHAPE", -3: "GA_ERR_WORKSPACE", -4: "GA_ERR_LAUNCH", -5: "GA_ERR_BAD_FLAGS"}
+GA_SURFEL_STORE_PLAIN, GA_SURFEL_STORE_WRITE_THROUGH, GA_SURFEL_STORE_NONTEMPORAL = 0, 1, 2
+
+
+def store_flags(pre: int = 0, fill: int = 0, sort: int = 0, blend: int = 0) -> int:
+    """include/ga_surfel.h: GA_SURFEL_STORE_FLAGS -- the store-policy field of GaSurfelForwardArgs.flags (bits 4..11, two per site)"""
+    return ((pre & 3) | ((fill & 3) << 2) | ((sort & 3) << 4) | ((blend & 3) << 6)) << 4
+
+
+GA_SURFEL_STORE_DEFAULT = store_flags(0, 0, 0, 0)   # include/ga_surfel.h: the measured choice (profiles/store_policy_ab.txt)
+
 
 
 class GaSurfelForwardArgs(ctypes.Structure):
@@ -119,7 +129,7 @@ GA_FPS_VARIANT_REGISTER, GA_FPS_VARIANT_STREAMING = 0, 1
 GA_PC_KNN_MAX_K = 32
 
 EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspace_layout2", "ga_surfel_forward", "ga_surfel_postprocess",
-           "ga_surfel_backward", "ga_surfel_backward_scratch_bytes",
+           "ga_surfel_backward", "ga_surfel_backward_scratch_bytes", "ga_surfel_store_policy",
            "ga_tsdf_integrate", "ga_tsdf_mesh_scratch_bytes", "ga_tsdf_mesh_count", "ga_tsdf_mesh_emit", "ga_mesh_write_obj", "ga_mesh_cluster_labels",
            "ga_pc_fps", "ga_pc_fps_plan", "ga_pc_fps_workspace_bytes", "ga_pc_nearest",
            "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward")
@@ -159,6 +169,8 @@ def lib():
                                                                         ctypes.POINTER(GaSurfelWorkspaceLayout)]
         L.ga_surfel_forward.restype = ctypes.c_int
         L.ga_surfel_forward.argtypes = [ctypes.POINTER(GaSurfelForwardArgs), ctypes.c_void_p]
+        L.ga_surfel_store_policy.restype = ctypes.c_int
+        L.ga_surfel_store_policy.argtypes = [ctypes.c_int32, ctypes.POINTER(ctypes.c_int32 * 4)]
         L.ga_surfel_backward.restype = ctypes.c_int
         L.ga_surfel_backward.argtypes = [ctypes.POINTER(GaSurfelBackwardArgs), ctypes.c_void_p]
         L.ga_surfel_backward_scratch_bytes.restype = ctypes.c_size_t

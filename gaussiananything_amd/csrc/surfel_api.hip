@@ -22,6 +22,23 @@ bool make_dims(int32_t N, int32_t V, int32_t H, int32_t W, ga::Dims *d)
     return true;
 }
 
+// GA_SURFEL_STORE = "PFSB", one digit 0..2 per site (include/ga_surfel.h), read once: the store-policy field it replaces in the
+// flags of every forward; -1 = not set, -2 = set to something else (every forward then fails with GA_ERR_BAD_FLAGS)
+int store_override()
+{
+    static const int field = [] {
+        const char *e = getenv("GA_SURFEL_STORE");
+        if (!e || !*e) return -1;
+        int f = 0;
+        for (int site = 0; site < GA_SURFEL_STORE_SITES; ++site) {
+            if (e[site] < '0' || e[site] > '2') return -2;
+            f |= (e[site] - '0') << (GA_SURFEL_STORE_SHIFT + 2 * site);
+        }
+        return e[GA_SURFEL_STORE_SITES] ? -2 : f;
+    }();
+    return field;
+}
+
 }  // namespace
 
 extern "C" {
@@ -63,9 +80,26 @@ int ga_surfel_workspace_layout2(int32_t num_points, int32_t num_views, int32_t i
     return GA_OK;
 }
 
-int ga_surfel_forward(const GaSurfelForwardArgs *a, void *stream_v)
+int ga_surfel_store_policy(int32_t flags, int32_t policy[GA_SURFEL_STORE_SITES])
 {
-    if (!a) return GA_ERR_NULL_ARG;
+    if (!policy) return GA_ERR_NULL_ARG;
+    for (int site = 0; site < GA_SURFEL_STORE_SITES; ++site)
+        if (ga::store_site(flags, site) == 3) return GA_ERR_BAD_FLAGS;
+    for (int site = 0; site < GA_SURFEL_STORE_SITES; ++site) policy[site] = ga::store_site(flags, site);
+    return GA_OK;
+}
+
+int ga_surfel_forward(const GaSurfelForwardArgs *args, void *stream_v)
+{
+    if (!args) return GA_ERR_NULL_ARG;
+    // the store policies are decoded once, here: the launches below take their site's two bits from the (possibly overridden) flags
+    GaSurfelForwardArgs with_policy = *args;
+    const int over = store_override();
+    if (over == -2) return GA_ERR_BAD_FLAGS;
+    if (over >= 0) with_policy.flags = (args->flags & ~GA_SURFEL_STORE_MASK) | over;
+    int32_t policy[GA_SURFEL_STORE_SITES];
+    if (ga_surfel_store_policy(with_policy.flags, policy) != GA_OK) return GA_ERR_BAD_FLAGS;
+    const GaSurfelForwardArgs *a = &with_policy;
     ga::Dims d;
     if (!make_dims(a->num_points, a->num_views, a->image_height, a->image_width, &d)) return GA_ERR_BAD_SHAPE;
     GaSurfelWorkspaceLayout L;

@@ -50,6 +50,9 @@ struct ScanArgs {
     int64_t capacity, seg_capacity;
     uint32_t *__restrict__ seg_table;
     int64_t *__restrict__ status;
+    int pol;   // store policy of the FILL site (the fused fill + schedule launch; the single-workgroup scan re-reads what it wrote and stores plainly).
+               // The kernels that store under a policy exist twice: kPol = false has every store plain at compile time (the selection in
+               // gstore folds away), kPol = true takes the policy from its arguments
 };
 
 // kOwnLaunch (the only instantiation left): the scan is a launch of its own in front of the fill -- problems beyond the sizes
@@ -294,13 +297,14 @@ __global__ __launch_bounds__(1024) void surfel_tile_scan_kernel(ScanArgs a) { ti
 //      c) every entry takes its rank inside the workgroup from a returning LDS atomic and writes its key.
 //    The order inside a segment is arbitrary (the per-tile sort fixes it).  Views with more than kLdsTiles tiles fall
 //    back to one returning global atomic per entry.
-template <bool kLds>
+template <bool kLds, bool kPol>
 __global__ __launch_bounds__(256) void surfel_fill_kernel(const uint16_t *__restrict__ rect,
                                                           const float *__restrict__ depth, Dims dm,
                                                           uint32_t *__restrict__ tile_cursor,
                                                           uint64_t *__restrict__ keys,
-                                                          const int64_t *__restrict__ status)
+                                                          const int64_t *__restrict__ status, int pol_arg)
 {
+    const int pol = kPol ? pol_arg : kStorePlain;
     extern __shared__ uint32_t lds[];  // [tiles] counts -> ranks, [tiles] segment bases
     if (status[GA_STATUS_OVERFLOW]) return;
     const int v = blockIdx.y;
@@ -336,7 +340,7 @@ __global__ __launch_bounds__(256) void surfel_fill_kernel(const uint16_t *__rest
             for (int tx = rc.x; tx < rc.z; ++tx) {
                 const int t = ty * dm.gx + tx;
                 const uint32_t pos = kLds ? basep[t] + atomicAdd(cnt + t, 1u) : atomicAdd(cur + t, 1u);
-                keys[pos] = key;
+                gstore(keys + pos, key, pol);
             }
     }
 }
@@ -372,7 +376,7 @@ struct FillStamp {
 };
 #endif
 
-__device__ __forceinline__ void schedule_slice(const ScanArgs &sa, int nall, int nsched, uint32_t *__restrict__ big_scratch)
+__device__ __forceinline__ void schedule_slice(const ScanArgs &sa, int nall, int nsched, uint32_t *__restrict__ big_scratch, int pol)
 {
     __shared__ uint32_t histl[kClasses][64];     // one copy per lane: low half = tiles of class b, high half = those in front of my slice
     __shared__ uint32_t cls_all[kClasses], cls_before[kClasses], cls_start[kClasses], cls_work[kClasses], slice_cnt[kClasses];
@@ -479,14 +483,14 @@ __device__ __forceinline__ void schedule_slice(const ScanArgs &sa, int nall, int
             const uint32_t beg = carry + wbase + x - c;
             const int b = length_class(c);
             const uint32_t pos = cls_start[b] + cls_before[b] + atomicAdd(&slice_cnt[b], 1u);
-            sa.tile_order[pos] = make_uint4((uint32_t)gi, beg, c, 0u);
-            sa.tile_start[gi] = beg;
+            gstore(sa.tile_order + pos, make_uint4((uint32_t)gi, beg, c, 0u), pol);
+            gstore(sa.tile_start + gi, beg, pol);
             if (c > (uint32_t)kSortCap) {   // runs 1.. of a list longer than one sort run: table slots in the order of the tile index
                 uint32_t dst = 0;
                 for (uint32_t q = 0; q < nbig; ++q)
                     if (big_i[q] < (uint32_t)gi) dst += (big_c[q] - 1u) / kSortCap;
                 for (uint32_t r = 1; r <= (c - 1u) / kSortCap; ++r, ++dst)
-                    if (dst < table_cap) sa.run_table[dst] = make_uint4(pos, r, beg, c);
+                    if (dst < table_cap) gstore(sa.run_table + dst, make_uint4(pos, r, beg, c), pol);
             }
         }
         carry += round;
@@ -502,7 +506,7 @@ __device__ __forceinline__ void schedule_slice(const ScanArgs &sa, int nall, int
         if (tid == 0) {
             uint32_t extra = 0;
             for (uint32_t q = 0; q < nbig; ++q) extra += (big_c[q] - 1u) / kSortCap;
-            sa.tile_start[nall] = (uint32_t)total;
+            gstore(sa.tile_start + nall, (uint32_t)total, pol);
             sa.status[GA_STATUS_NUM_RENDERED] = (int64_t)total;
             sa.status[GA_STATUS_OVERFLOW] = overflow ? 1 : 0;
             sa.status[GA_STATUS_MAX_TILE] = (int64_t)mx;
@@ -517,6 +521,7 @@ __device__ __forceinline__ void schedule_slice(const ScanArgs &sa, int nall, int
     }
 }
 
+template <bool kPol>
 __global__ __launch_bounds__(kFT) void surfel_fill_sched_kernel(ScanArgs sa, const uint16_t *__restrict__ rect,
                                                                  const float *__restrict__ depth, Dims dm,
                                                                  const unsigned long long *__restrict__ view_total,
@@ -524,11 +529,12 @@ __global__ __launch_bounds__(kFT) void surfel_fill_sched_kernel(ScanArgs sa, con
                                                                  unsigned long long *__restrict__ dbg)
 {
     extern __shared__ uint32_t lds[];  // [tiles] counts -> ranks, [tiles] list begins -> segment bases of this workgroup
+    const int pol = kPol ? sa.pol : kStorePlain;
 #ifdef GA_FILL_STAMPS
     FillStamp stamp{dbg + 3300000 + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4, __builtin_amdgcn_s_memrealtime()};   // (behind the words the blend's segments use at BASELINE configs[1])
 #endif
     if (blockIdx.y == 0) {
-        if ((int)blockIdx.x < nsched) schedule_slice(sa, dm.V * dm.tiles, nsched, big_scratch);
+        if ((int)blockIdx.x < nsched) schedule_slice(sa, dm.V * dm.tiles, nsched, big_scratch, pol);
         return;
     }
     __shared__ uint32_t wave_sum[kFW];
@@ -619,7 +625,7 @@ __global__ __launch_bounds__(kFT) void surfel_fill_sched_kernel(ScanArgs sa, con
         for (int ty = rc.y; ty < rc.w; ++ty)
             for (int tx = rc.x; tx < rc.z; ++tx) {
                 const int t = ty * dm.gx + tx;
-                keys[basep[t] + atomicAdd(cnt + t, 1u)] = key;
+                gstore(keys + (basep[t] + atomicAdd(cnt + t, 1u)), key, pol);
             }
     }
 }
@@ -877,7 +883,7 @@ __device__ __forceinline__ void wave_blocks(unsigned long long (&key)[E], int la
 
 // sort keys[beg, beg + n) (n <= 64 E) into point_list
 template <int E>
-__device__ __forceinline__ void wave_sort_list(const uint64_t *__restrict__ keys, uint32_t *__restrict__ point_list, uint32_t beg, int n, int lane)
+__device__ __forceinline__ void wave_sort_list(const uint64_t *__restrict__ keys, uint32_t *__restrict__ point_list, uint32_t beg, int n, int lane, int pol)
 {
     unsigned long long key[E];
 #pragma unroll
@@ -889,7 +895,7 @@ __device__ __forceinline__ void wave_sort_list(const uint64_t *__restrict__ keys
 #pragma unroll
     for (int m = 0; m < E; ++m) {
         const int t = lane * E + m;
-        if (t < n) point_list[beg + t] = (uint32_t)key[m];
+        if (t < n) gstore(point_list + (beg + t), (uint32_t)key[m], pol);
     }
 }
 
@@ -920,7 +926,7 @@ __device__ __forceinline__ bool sort_block_assignment(const uint4 *__restrict__ 
 constexpr int kMergeParts = 4;
 
 __device__ __forceinline__ void merge_runs(uint64_t *__restrict__ other, const uint64_t *__restrict__ keys, uint32_t *__restrict__ point_list,
-                                           const uint32_t *__restrict__ run_count, uint32_t run, uint32_t beg, int n, int part)
+                                           const uint32_t *__restrict__ run_count, uint32_t run, uint32_t beg, int n, int part, int pol)
 {
     const int nruns = (n + kSortCap - 1) / kSortCap;
     if (threadIdx.x == 0)
@@ -972,7 +978,7 @@ __device__ __forceinline__ void merge_runs(uint64_t *__restrict__ other, const u
 #pragma unroll
     for (int i = 0; i < kPer; ++i) {
         const int e = part * (kSortCap / kMergeParts) + (int)threadIdx.x + 256 * i;
-        if (e < rn) point_list[beg + rank[i]] = (uint32_t)mine[i];
+        if (e < rn) gstore(point_list + (beg + rank[i]), (uint32_t)mine[i], pol);
     }
 }
 
@@ -984,6 +990,7 @@ __device__ __forceinline__ void merge_runs(uint64_t *__restrict__ other, const u
 // their workgroups (three quarters of all keys, 17 .. 24 us of life each, four of them per CU at a time); one wave per list of ANY length
 // (32 keys per lane for a 2048-key run: 64-bit cross-lane stages cost ~30 cycles per key, a single wave's chain was 30 .. 40 us) was
 // built and measured: 53 us instead of 36 for sort + merge -- not kept.
+template <bool kPol>
 __global__ __launch_bounds__(256) void surfel_run_sort_kernel(const uint4 *__restrict__ tile_order,
                                                               const uint4 *__restrict__ run_table,
                                                               uint32_t max_extra, uint32_t nbig, uint32_t nslots,
@@ -994,8 +1001,10 @@ __global__ __launch_bounds__(256) void surfel_run_sort_kernel(const uint4 *__res
                                                               unsigned long long *__restrict__ view_total, int nviews,
                                                               uint32_t *__restrict__ seg_sync, unsigned long long *__restrict__ dbg,
                                                               Dims dm, const float *__restrict__ bg, float *__restrict__ out_color,
-                                                              float *__restrict__ out_others)
+                                                              float *__restrict__ out_others, int pol_arg)
 {
+    const int pol_bg = kPol ? pol_arg : kStorePlain;
+    const int pol = pol_bg == kStoreNT ? kStorePlain : pol_bg;   // point_list: the blend gathers it right behind this launch
     __shared__ __attribute__((aligned(16))) double s[kSortCap];  // raw key bits (see bitonic_sort_blocked)
     const int tid = threadIdx.x;
 #ifdef GA_SORT_STAMPS   // measurement build: (start, end, list length) per wave in the (dead by now) depth array, 100 MHz clock
@@ -1017,7 +1026,7 @@ __global__ __launch_bounds__(256) void surfel_run_sort_kernel(const uint4 *__res
         if (!sort_block_assignment(tile_order, run_table, status, max_extra, b, run, beg, n)) return;
         if (n <= kSortCap) return;
         merge_runs(reinterpret_cast<uint64_t *>(s), keys, point_list, seg_sync + 8 * (size_t)pos + 5, run, beg, n,
-                   (int)((blockIdx.x - nsort) % kMergeParts));
+                   (int)((blockIdx.x - nsort) % kMergeParts), pol);
         return;
     }
     if (blockIdx.x >= max_extra + nbig) {
@@ -1047,26 +1056,26 @@ __global__ __launch_bounds__(256) void surfel_run_sort_kernel(const uint4 *__res
                 float *oc = out_color + (size_t)v * 3 * HW + pid, *oo = out_others + (size_t)v * 7 * HW + pid;
                 const float b0 = bg[0], b1 = bg[1], b2 = bg[2];
                 if (px + 3 < dm.W && (dm.W & 3) == 0 && (HW & 3) == 0) {   // 16-byte stores: whole 64-byte tile rows per four lanes
-                    *reinterpret_cast<float4 *>(oc) = make_float4(b0, b0, b0, b0);
-                    *reinterpret_cast<float4 *>(oc + HW) = make_float4(b1, b1, b1, b1);
-                    *reinterpret_cast<float4 *>(oc + 2 * HW) = make_float4(b2, b2, b2, b2);
+                    gstore(reinterpret_cast<float4 *>(oc), make_float4(b0, b0, b0, b0), pol_bg);
+                    gstore(reinterpret_cast<float4 *>(oc + HW), make_float4(b1, b1, b1, b1), pol_bg);
+                    gstore(reinterpret_cast<float4 *>(oc + 2 * HW), make_float4(b2, b2, b2, b2), pol_bg);
 #pragma unroll
-                    for (int c = 0; c < 7; ++c) *reinterpret_cast<float4 *>(oo + (size_t)c * HW) = make_float4(0.f, 0.f, 0.f, 0.f);
+                    for (int c = 0; c < 7; ++c) gstore(reinterpret_cast<float4 *>(oo + (size_t)c * HW), make_float4(0.f, 0.f, 0.f, 0.f), pol_bg);
                 } else {
                     for (int e = 0; e < 4 && px + e < dm.W; ++e) {
-                        oc[e] = b0; oc[HW + e] = b1; oc[2 * HW + e] = b2;
-                        for (int c = 0; c < 7; ++c) oo[(size_t)c * HW + e] = 0.f;
+                        gstore(oc + e, b0, pol_bg); gstore(oc + HW + e, b1, pol_bg); gstore(oc + 2 * HW + e, b2, pol_bg);
+                        for (int c = 0; c < 7; ++c) gstore(oo + (size_t)c * HW + e, 0.f, pol_bg);
                     }
                 }
             }
             return;
         }
         if (overflow || n <= 0 || n >= kWaveSort) return;
-        if (n == 1) { if (lane == 0) point_list[beg] = (uint32_t)keys[beg]; return; }
-        if (n <= 64) wave_sort_list<1>(keys, point_list, beg, n, lane);
-        else if (n <= 128) wave_sort_list<2>(keys, point_list, beg, n, lane);
-        else if (n <= 256) wave_sort_list<4>(keys, point_list, beg, n, lane);
-        else wave_sort_list<8>(keys, point_list, beg, n, lane);
+        if (n == 1) { if (lane == 0) gstore(point_list + beg, (uint32_t)keys[beg], pol); return; }
+        if (n <= 64) wave_sort_list<1>(keys, point_list, beg, n, lane, pol);
+        else if (n <= 128) wave_sort_list<2>(keys, point_list, beg, n, lane, pol);
+        else if (n <= 256) wave_sort_list<4>(keys, point_list, beg, n, lane, pol);
+        else wave_sort_list<8>(keys, point_list, beg, n, lane, pol);
         return;
     }
     uint32_t run, beg;
@@ -1081,7 +1090,7 @@ __global__ __launch_bounds__(256) void surfel_run_sort_kernel(const uint4 *__res
     __syncthreads();
     bitonic_sort_lds(s, np, tid);
     if (n <= kSortCap) {
-        for (int t = tid; t < rn; t += 256) point_list[beg + t] = (uint32_t)__double_as_longlong(s[sort_slot(t)]);   // single run: final order
+        for (int t = tid; t < rn; t += 256) gstore(point_list + (beg + t), (uint32_t)__double_as_longlong(s[sort_slot(t)]), pol);   // single run: final order
     } else {
         // sorted run: merged by the last grid region (other workgroups, possibly on another XCD: see merge_runs)
         for (int t = tid; t < rn; t += 256)
@@ -1096,7 +1105,9 @@ void launch_binning(const GaSurfelForwardArgs &a, const Dims &d, const Workspace
 {
     const int nt = d.V * d.tiles;
     const ScanArgs sa{ws.tile_count, ws.seg_sync, (uint32_t)(8 * ((size_t)a.capacity / 1024 + 1)), ws.tile_start, ws.tile_cursor,
-                      ws.tile_order, ws.run_table, nt, a.capacity, seg_items(a.capacity, a.seg_capacity), ws.seg_table, ws.status};
+                      ws.tile_order, ws.run_table, nt, a.capacity, seg_items(a.capacity, a.seg_capacity), ws.seg_table, ws.status,
+                      store_site(a.flags, GA_SURFEL_STORE_SITE_FILL)};
+    const bool policy = sa.pol != kStorePlain;
     const unsigned nbx = (unsigned)std::max(1, (d.N + kFT * kFillSplats - 1) / (kFT * kFillSplats));
     const int nsched = (int)std::min<unsigned>(nbx, (unsigned)((nt + kFT - 1) / kFT));   // one schedule slot per thread of a row-0 workgroup
     // (16-bit halves in the schedule's class bins; the schedule workgroups' notes of the long lists fit point_list)
@@ -1110,8 +1121,10 @@ void launch_binning(const GaSurfelForwardArgs &a, const Dims &d, const Workspace
     uint8_t st = dev == di ? lds_optin[di].load(std::memory_order_acquire) : (uint8_t)0;
     if (st == 0) {
         const int want = 2 * kLdsTiles * (int)sizeof(uint32_t);
-        const bool ok = hipFuncSetAttribute((const void *)surfel_fill_sched_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess &&
-                        hipFuncSetAttribute((const void *)surfel_fill_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess;
+        bool ok = true;
+        for (const void *f : {(const void *)surfel_fill_sched_kernel<false>, (const void *)surfel_fill_sched_kernel<true>,
+                              (const void *)surfel_fill_kernel<true, false>, (const void *)surfel_fill_kernel<true, true>})
+            ok = ok && hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, want) == hipSuccess;
         if (!ok) (void)hipGetLastError();
         st = ok ? 1 : 2;
         lds_optin[di].store(st, std::memory_order_release);
@@ -1120,18 +1133,22 @@ void launch_binning(const GaSurfelForwardArgs &a, const Dims &d, const Workspace
     const size_t dyn = 2 * (size_t)d.tiles * sizeof(uint32_t);
     const bool fused_fits = st == 1 || dyn + 12288 <= 65536, fill_fits = st == 1 || dyn + 1024 <= 65536;
     if (fused_fits && d.tiles <= kLdsTiles && nt <= 0xFFFF && (int64_t)nsched * 2 * (a.capacity / kSortCap + 1) <= a.capacity) {
-        hipLaunchKernelGGL(surfel_fill_sched_kernel, dim3(nbx, (unsigned)d.V + 1u), dim3(kFT), dyn, s, sa,
-                           ws.rect, ws.depth, d, ws.view_total, ws.keys, nsched, ws.point_list, ws.seg_scratch);
+        if (policy)
+            hipLaunchKernelGGL(surfel_fill_sched_kernel<true>, dim3(nbx, (unsigned)d.V + 1u), dim3(kFT), dyn, s, sa,
+                               ws.rect, ws.depth, d, ws.view_total, ws.keys, nsched, ws.point_list, ws.seg_scratch);
+        else
+            hipLaunchKernelGGL(surfel_fill_sched_kernel<false>, dim3(nbx, (unsigned)d.V + 1u), dim3(kFT), dyn, s, sa,
+                               ws.rect, ws.depth, d, ws.view_total, ws.keys, nsched, ws.point_list, ws.seg_scratch);
         return;
     }
     // larger problems: the single-workgroup scan in front of the fill
     hipLaunchKernelGGL(surfel_tile_scan_kernel, dim3(1), dim3(1024), 0, s, sa);
     const dim3 grid((unsigned)((d.N + 256 * kBinSplats - 1) / (256 * kBinSplats)), (unsigned)d.V);
-    if (d.tiles <= kLdsTiles && fill_fits)
-        hipLaunchKernelGGL(surfel_fill_kernel<true>, grid, dim3(256), dyn, s, ws.rect, ws.depth, d, ws.tile_cursor,
-                           ws.keys, ws.status);
-    else
-        hipLaunchKernelGGL(surfel_fill_kernel<false>, grid, dim3(256), 0, s, ws.rect, ws.depth, d, ws.tile_cursor, ws.keys, ws.status);
+#define GA_FILL_LAUNCH(L, P, DYN) \
+    hipLaunchKernelGGL((surfel_fill_kernel<L, P>), grid, dim3(256), DYN, s, ws.rect, ws.depth, d, ws.tile_cursor, ws.keys, ws.status, sa.pol)
+    if (d.tiles <= kLdsTiles && fill_fits) { if (policy) GA_FILL_LAUNCH(true, true, dyn); else GA_FILL_LAUNCH(true, false, dyn); }
+    else { if (policy) GA_FILL_LAUNCH(false, true, 0); else GA_FILL_LAUNCH(false, false, 0); }
+#undef GA_FILL_LAUNCH
 }
 
 void launch_tile_sort(const GaSurfelForwardArgs &a, const Dims &d, const Workspace &ws, hipStream_t s)
@@ -1141,10 +1158,14 @@ void launch_tile_sort(const GaSurfelForwardArgs &a, const Dims &d, const Workspa
     const uint32_t nbig = (uint32_t)std::min<int64_t>(nt, a.capacity / kWaveSort + 1);   // lists of kWaveSort entries or more
     // lists longer than one run sit at the front of tile_order and there are fewer than capacity / kSortCap of them
     const uint32_t max_big = (uint32_t)std::min<int64_t>(nt, a.capacity / kSortCap);
-    hipLaunchKernelGGL(surfel_run_sort_kernel, dim3(max_extra + nbig + (nt + 3) / 4 + (max_big + max_extra) * kMergeParts), dim3(256), 0, s,
-                       ws.tile_order, ws.run_table, max_extra, nbig, nt, ws.keys, ws.point_list, ws.status, ws.tile_count, ws.tile_cursor,
-                       ws.view_total, d.V, ws.seg_sync, reinterpret_cast<unsigned long long *>(ws.depth), d, a.bg,
-                       (a.flags & GA_SURFEL_FLAG_BG_IN_BLEND) ? nullptr : a.out_color, a.out_others);
+    const int pol = store_site(a.flags, GA_SURFEL_STORE_SITE_SORT);
+#define GA_SORT_LAUNCH(P)                                                                                                                       \
+    hipLaunchKernelGGL(surfel_run_sort_kernel<P>, dim3(max_extra + nbig + (nt + 3) / 4 + (max_big + max_extra) * kMergeParts), dim3(256), 0, s, \
+                       ws.tile_order, ws.run_table, max_extra, nbig, nt, ws.keys, ws.point_list, ws.status, ws.tile_count, ws.tile_cursor,      \
+                       ws.view_total, d.V, ws.seg_sync, reinterpret_cast<unsigned long long *>(ws.depth), d, a.bg,                              \
+                       (a.flags & GA_SURFEL_FLAG_BG_IN_BLEND) ? nullptr : a.out_color, a.out_others, pol)
+    if (pol != kStorePlain) GA_SORT_LAUNCH(true); else GA_SORT_LAUNCH(false);
+#undef GA_SORT_LAUNCH
 }
 
 }  // namespace ga

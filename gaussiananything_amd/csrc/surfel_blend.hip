@@ -405,7 +405,7 @@ __device__ __forceinline__ void consume(Ring &ring, const Consumer &c, uint32_t 
         ++st.chunks;
         trips((int)((i + kItemChunks - 1) % kItemChunks) * 64, slot * 64, bstep);   // until every lane has finished the previous chunk
         if (bstep)   // (a lane that has not reached the new chunk yet enters it with what it has now)
-            tseg[(size_t)((gc0 + i) >> 1) * 256] = snapped ? Tsnap : (done ? -1.0f : a.T);
+            gstore(tseg + (size_t)((gc0 + i) >> 1) * 256, snapped ? Tsnap : (done ? -1.0f : a.T), store_site(flags, GA_SURFEL_STORE_SITE_BLEND));
         cur = nxt;           // what is left of this chunk becomes the "previous chunk" of the next step
         nxt = 0;
         if (WRAP) {          // chunks < i are finished: their slots may be reused
@@ -416,7 +416,7 @@ __device__ __forceinline__ void consume(Ring &ring, const Consumer &c, uint32_t 
     trips((int)((i + kItemChunks - 1) % kItemChunks) * 64, 0);  // drain: `cur` is the last fetched chunk, `nxt` is empty
     if (STORE)   // (left the loop early: every pixel's walk has ended)
         for (uint32_t j = i; j < nch; ++j)
-            if (((gc0 + j) & 1u) == 0u) tseg[(size_t)((gc0 + j) >> 1) * 256] = -1.0f;
+            if (((gc0 + j) & 1u) == 0u) gstore(tseg + (size_t)((gc0 + j) >> 1) * 256, -1.0f, store_site(flags, GA_SURFEL_STORE_SITE_BLEND));
     if (flags & GA_SURFEL_FLAG_STATS) {
         for (int o = 32; o > 0; o >>= 1) mine = max(mine, (unsigned)__shfl_xor(mine, o, 64));
         st.lanemax += mine;
@@ -430,21 +430,22 @@ __device__ __forceinline__ void consume(Ring &ring, const Consumer &c, uint32_t 
 }
 
 __device__ __forceinline__ void write_pixel(const PixelAcc &a, const float *__restrict__ bg, const Dims &dm, int v, int pxi,
-                                            int pyi, float *__restrict__ out_color, float *__restrict__ out_others)
+                                            int pyi, float *__restrict__ out_color, float *__restrict__ out_others, int flags)
 {
     const size_t HW = (size_t)dm.H * dm.W, pid = (size_t)pyi * dm.W + pxi;
     float *oc = out_color + (size_t)v * 3 * HW + pid;
     float *oo = out_others + (size_t)v * 7 * HW + pid;
-    oc[0] = a.N2C0.y + a.T * bg[0];
-    oc[HW] = a.C12.x + a.T * bg[1];
-    oc[2 * HW] = a.C12.y + a.T * bg[2];
-    oo[0] = a.Dp;
-    oo[HW] = 1.0f - a.T;
-    oo[2 * HW] = a.N01.x;
-    oo[3 * HW] = a.N01.y;
-    oo[4 * HW] = a.N2C0.x;
-    oo[5 * HW] = a.median;
-    oo[6 * HW] = a.dist;
+    const int pol = store_site(flags, GA_SURFEL_STORE_SITE_BLEND);
+    gstore(oc, a.N2C0.y + a.T * bg[0], pol);
+    gstore(oc + HW, a.C12.x + a.T * bg[1], pol);
+    gstore(oc + 2 * HW, a.C12.y + a.T * bg[2], pol);
+    gstore(oo, a.Dp, pol);
+    gstore(oo + HW, 1.0f - a.T, pol);
+    gstore(oo + 2 * HW, a.N01.x, pol);
+    gstore(oo + 3 * HW, a.N01.y, pol);
+    gstore(oo + 4 * HW, a.N2C0.x, pol);
+    gstore(oo + 5 * HW, a.median, pol);
+    gstore(oo + 6 * HW, a.dist, pol);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -495,7 +496,7 @@ __device__ __forceinline__ void finish_segment(const BlendArgs &k, const Dims &d
             dead = tt[12] != 0.0f;
         }
     }
-    if (inside) write_pixel(r, k.bg, dm, v, pxi, pyi, k.out_color, k.out_others);
+    if (inside) write_pixel(r, k.bg, dm, v, pxi, pyi, k.out_color, k.out_others, k.flags);
 }
 
 template <bool STORE>
@@ -538,7 +539,7 @@ __device__ __forceinline__ void blend_item(Ring &ring, const BlendArgs &k, const
         const int px = wave * 64 + lane;
         if (STORE)
             for (uint32_t gc = c0; gc < c1; ++gc)
-                if ((gc & 1u) == 0u) tseg[(size_t)(gc >> 1) * 256] = -1.0f;
+                if ((gc & 1u) == 0u) gstore(tseg + (size_t)(gc >> 1) * 256, -1.0f, store_site(flags, GA_SURFEL_STORE_SITE_BLEND));
         if (!last_seg) xwg_store(seg_scratch + (size_t)work * kSegFloats + px, 0.0f, epoch);
         finish_segment(k, dm, lane, pos, work - seg * wstride, wstride, nsegs, px, v, pxi, pyi, pxi < dm.W && pyi < dm.H,
                        seg_sync + 8 * (size_t)pos + wave);
@@ -575,7 +576,7 @@ __device__ __forceinline__ void blend_item(Ring &ring, const BlendArgs &k, const
     if (nsegs == 1) {
         if (wraps) consume<true, true, STORE>(ring, c, nch, a, done, st, flags, duty, tseg, 0u);
         else consume<true, false, STORE>(ring, c, nch, a, done, st, flags, duty, tseg, 0u);
-        if (inside) write_pixel(a, bg, dm, v, pxi, pyi, out_color, out_others);
+        if (inside) write_pixel(a, bg, dm, v, pxi, pyi, out_color, out_others, flags);
     } else {
         const uint32_t work0 = work - seg * wstride;            // work item of segment 0 of this tile (segment k: + k * wstride)
         const int px = wave * 64 + lane;                        // pixel index inside the scratch records
@@ -1025,7 +1026,7 @@ __device__ __forceinline__ void blend_tile_split(Ring2 &ring, const BlendArgs &k
     GA_LDS_ORDER();
     if (lane == 0) { lds_store(&ring.doneA[wave], kGone); lds_store(&ring.doneB[wave], kGone); }
     GA_LDS_ORDER();
-    if (inside) write_pixel(a, k.bg, dm, v, pxi, pyi, k.out_color, k.out_others);
+    if (inside) write_pixel(a, k.bg, dm, v, pxi, pyi, k.out_color, k.out_others, k.flags);
     GA_PROF(4);
     while (duty.next < nch && duty_stage2(ring, duty, lane, nch)) {}   // the others may still need my chunks
     GA_PROF(6);
@@ -1053,7 +1054,9 @@ __device__ __forceinline__ void blend_tile_split(Ring2 &ring, const BlendArgs &k
 #ifndef GA_BLEND_XCD_RUNS
 #define GA_BLEND_XCD_RUNS 3   // log2 of the run length (0: off)
 #endif
-template <bool STORE>
+// POLICY = false: every store plain, decided at compile time (the store-policy bits of k.flags are known to be zero below, so the
+// selection in gstore folds away and the kernel is the one without the switch); true: the BLEND site's policy from k.flags at run time
+template <bool STORE, bool POLICY>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GA_BLEND_WAVES, GA_BLEND_WAVES))) void surfel_blend_kernel(BlendArgs k, Dims dm, int ntiles,
                                                            uint32_t seg_region,
                                                            const uint32_t *__restrict__ seg_table,
@@ -1062,6 +1065,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GA_BLEND_WA
     // one LDS allocation, two images: the fused walk's ring (segments, the differentiable forward) / the split walk's
     __shared__ __attribute__((aligned(16))) unsigned char lds_image[sizeof(Ring) > sizeof(Ring2) ? sizeof(Ring) : sizeof(Ring2)];
     Ring &ring = *reinterpret_cast<Ring *>(lds_image);
+    if (!POLICY) k.flags &= ~GA_SURFEL_STORE_MASK;
     // (requested before the status words are looked at: on overflow the entry is stale but the slot exists)
     // schedule slot of a tile workgroup: runs of 2^GA_BLEND_XCD_RUNS consecutive slots -- tiles of one view and one pair of tile rows that
     // fall into the same length class (the order the tile scan leaves inside a class) -- go to workgroups eight apart, i.e.
@@ -1139,7 +1143,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GA_BLEND_WA
             if (!(k.flags & GA_SURFEL_FLAG_BG_IN_BLEND)) return;   // (round 6: written by the sort launch's waves, surfel_bin.hip)
             const int v = (int)(my_sched.x / (uint32_t)dm.tiles), tile = (int)(my_sched.x - (uint32_t)v * dm.tiles);
             const int pxi = (tile % dm.gx) * kTile + (wave & 1) * 8 + (lane & 7), pyi = (tile / dm.gx) * kTile + (wave >> 1) * 8 + (lane >> 3);
-            if (pxi < dm.W && pyi < dm.H) write_pixel(fresh_pixel(1.0f), k.bg, dm, v, pxi, pyi, k.out_color, k.out_others);
+            if (pxi < dm.W && pyi < dm.H) write_pixel(fresh_pixel(1.0f), k.bg, dm, v, pxi, pyi, k.out_color, k.out_others, k.flags);
             return;
         }
 #if GA_BLEND_SPLIT
@@ -1187,12 +1191,13 @@ void launch_blend(const GaSurfelForwardArgs &a, const Dims &d, const Workspace &
     const uint32_t seg_region = (uint32_t)std::min<int64_t>(a.capacity / 256, kSegWGs);
     const BlendArgs k{ws.tile_order, ws.point_list, ws.record, a.bg, ws.seg_sync, ws.seg_scratch, a.out_color, a.out_others,
                       0u /* the segment workgroups read the launch epoch from the workspace */, a.flags, a.seg_T, reinterpret_cast<int64_t *>(ws.depth)};
-    if (a.seg_T)
-        hipLaunchKernelGGL(surfel_blend_kernel<true>, dim3(seg_region + (unsigned)nt), dim3(256), 0, s, k, d, nt, seg_region,
-                           ws.seg_table, ws.status);
-    else
-        hipLaunchKernelGGL(surfel_blend_kernel<false>, dim3(seg_region + (unsigned)nt), dim3(256), 0, s, k, d, nt, seg_region,
-                           ws.seg_table, ws.status);
+    const bool policy = store_site(a.flags, GA_SURFEL_STORE_SITE_BLEND) != kStorePlain;
+#define GA_BLEND_LAUNCH(S, P)                                                                                                \
+    hipLaunchKernelGGL((surfel_blend_kernel<S, P>), dim3(seg_region + (unsigned)nt), dim3(256), 0, s, k, d, nt, seg_region, \
+                       ws.seg_table, ws.status)
+    if (a.seg_T) { if (policy) GA_BLEND_LAUNCH(true, true); else GA_BLEND_LAUNCH(true, false); }
+    else { if (policy) GA_BLEND_LAUNCH(false, true); else GA_BLEND_LAUNCH(false, false); }
+#undef GA_BLEND_LAUNCH
 }
 
 }  // namespace ga

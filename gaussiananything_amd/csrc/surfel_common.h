@@ -97,6 +97,38 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nwg)
     return base + k;
 }
 
+// ---- global stores with a cache policy (GA_SURFEL_STORE_*, include/ga_surfel.h): 4, 8 and 16 bytes per lane.
+// A launch's site policy is wave-uniform (a kernel argument), so the selection is a scalar branch.  Write-through = an agent-scope
+// relaxed atomic store (global_store ... sc1); the compiler has no 16-byte atomic, so that size is written out -- with the
+// "memory" clobber that tells the compiler the statement writes memory, and the s_nop that keeps its next instruction off the data registers
+// until the store has read them.  Non-temporal = __builtin_nontemporal_store (nt).
+constexpr int kStorePlain = GA_SURFEL_STORE_PLAIN, kStoreWT = GA_SURFEL_STORE_WRITE_THROUGH, kStoreNT = GA_SURFEL_STORE_NONTEMPORAL;
+__host__ __device__ constexpr int store_site(int flags, int site) { return (flags >> (GA_SURFEL_STORE_SHIFT + 2 * site)) & 3; }
+
+template <typename T>
+__device__ __forceinline__ void gstore(T *p, const T &v, int policy)
+{
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8 || sizeof(T) == 16, "one dword, dwordx2 or dwordx4 store per lane");
+    if (policy == kStorePlain) { *p = v; return; }
+    if constexpr (sizeof(T) == 4) {
+        uint32_t b;
+        __builtin_memcpy(&b, &v, 4);
+        if (policy == kStoreWT) __hip_atomic_store(reinterpret_cast<uint32_t *>(p), b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else __builtin_nontemporal_store(b, reinterpret_cast<uint32_t *>(p));
+    } else if constexpr (sizeof(T) == 8) {
+        uint64_t b;
+        __builtin_memcpy(&b, &v, 8);
+        if (policy == kStoreWT) __hip_atomic_store(reinterpret_cast<uint64_t *>(p), b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else __builtin_nontemporal_store(b, reinterpret_cast<uint64_t *>(p));
+    } else {
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        u32x4 b;
+        __builtin_memcpy(&b, &v, 16);
+        if (policy == kStoreWT) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(p), "v"(b) : "memory");
+        else __builtin_nontemporal_store(b, reinterpret_cast<u32x4 *>(p));
+    }
+}
+
 void launch_preprocess(const GaSurfelForwardArgs &a, const Dims &d, const Workspace &ws, hipStream_t s);
 void launch_binning(const GaSurfelForwardArgs &a, const Dims &d, const Workspace &ws, hipStream_t s);
 void launch_tile_sort(const GaSurfelForwardArgs &a, const Dims &d, const Workspace &ws, hipStream_t s);

@@ -67,7 +67,7 @@ __device__ __forceinline__ SplatConst splat_constants(const float *__restrict__ 
 __device__ __forceinline__ bool preprocess_view(const SplatConst &c, const float *__restrict__ vm, const float *__restrict__ pm,
                                                 const Dims &dm, int64_t idx, int32_t *__restrict__ radii,
                                                 uint16_t *__restrict__ rect_out, float *__restrict__ depth_out, float4 *stg,
-                                                uint32_t *tc)
+                                                uint32_t *tc, int pol)
 {
     const float px = c.px, py = c.py, pz = c.pz;
     int radius_i = 0;
@@ -128,7 +128,7 @@ __device__ __forceinline__ bool preprocess_view(const SplatConst &c, const float
 
         live = true;
         radius_i = f2i(radius);
-        depth_out[idx] = vz;
+        gstore(depth_out + idx, vz, pol);
         rc = make_ushort4((unsigned short)rminx, (unsigned short)rminy, (unsigned short)rmaxx, (unsigned short)rmaxy);
 
         const float opa = c.opa;
@@ -192,8 +192,8 @@ __device__ __forceinline__ bool preprocess_view(const SplatConst &c, const float
         for (int ty = rminy; ty < rmaxy; ++ty)
             for (int tx = rminx; tx < rmaxx; ++tx) atomicAdd(tc + ty * dm.gx + tx, 1u);
     } while (false);
-    radii[idx] = radius_i;
-    *reinterpret_cast<ushort4 *>(rect_out + 4 * idx) = rc;
+    gstore(radii + idx, radius_i, pol);
+    gstore(reinterpret_cast<ushort4 *>(rect_out + 4 * idx), rc, pol);
     return live;
 }
 
@@ -202,15 +202,17 @@ __device__ __forceinline__ bool preprocess_view(const SplatConst &c, const float
 // tiles (vg * tiles words, <= 32 KiB) and flushed with one global atomic per touched tile per workgroup: the hottest tile of a real
 // scene receives thousands of increments per view and same-address L2 atomics serialise (measured 0.27 ms for 1.4 M increments,
 // profiles/r1a_*).  Views with more than kLdsTiles tiles use the global counters directly.
-template <bool kLds, int SPT>
+// kPol = false: every store plain, decided at compile time (the selection in gstore folds away); true: the policies in the arguments
+template <bool kLds, int SPT, bool kPol>
 __global__ __launch_bounds__(256) void surfel_preprocess_kernel(
     const float *__restrict__ means3D, const float *__restrict__ opacities, const float *__restrict__ colors,
     const float *__restrict__ scales, const float *__restrict__ rotations, const float *__restrict__ viewmatrix,
-    const float *__restrict__ projmatrix, float scale_modifier, Dims dm, int vg, int nt, int32_t *__restrict__ radii,
+    const float *__restrict__ projmatrix, float scale_modifier, Dims dm, int vg, int pol_arg, int pol_rec_arg, int32_t *__restrict__ radii,
     uint16_t *__restrict__ rect_out, float *__restrict__ depth_out,
     float *__restrict__ rec_out, uint32_t *__restrict__ tile_count, unsigned long long *__restrict__ view_total)
 {
     extern __shared__ uint32_t hist[];
+    const int pol = kPol ? pol_arg : kStorePlain, pol_rec = kPol ? pol_rec_arg : kStorePlain;
     // Records leave through LDS: a lane's record is 96 contiguous bytes, so direct stores would be six 16-byte pieces
     // at a 96-byte stride per instruction (partial lines); the wave's 64 records are one contiguous 6 KiB block, written
     // with six fully coalesced 1 KiB stores instead.
@@ -234,7 +236,7 @@ __global__ __launch_bounds__(256) void surfel_preprocess_kernel(
             bool live = false;
             if (mine)
                 live = preprocess_view(c, vm, pm, dm, (int64_t)v * dm.N + i, radii, rect_out, depth_out, wstage + lane * (kRec / 4),
-                                       kLds ? hist + (size_t)k * dm.tiles : tile_count + (size_t)v * dm.tiles);
+                                       kLds ? hist + (size_t)k * dm.tiles : tile_count + (size_t)v * dm.tiles, pol);
             if (__builtin_amdgcn_ballot_w64(live) != 0) {  // wave-uniform; records of culled lanes are never read
                 const int first = i - lane;                                    // first Gaussian of this wave
                 const int nq = min(64, dm.N - first) * (kRec / 4);             // float4s inside the array
@@ -242,11 +244,7 @@ __global__ __launch_bounds__(256) void surfel_preprocess_kernel(
 #pragma unroll
                 for (int j = 0; j < kRec / 4; ++j) {
                     const int q = lane + 64 * j;
-                    if (q < nq) {
-                        typedef float v4f __attribute__((ext_vector_type(4)));
-                        if (nt) __builtin_nontemporal_store(*reinterpret_cast<const v4f *>(wstage + q), reinterpret_cast<v4f *>(dst + q));
-                        else dst[q] = wstage[q];
-                    }
+                    if (q < nq) gstore(dst + q, wstage[q], pol_rec);
                 }
             }
         }
@@ -277,15 +275,18 @@ void launch_preprocess(const GaSurfelForwardArgs &a, const Dims &d, const Worksp
 {
     // views per workgroup: as many as keep the LDS histograms within 32 KiB (kLdsTiles words), at most GA_PRE_VIEWS
     static const int max_vg = [] { const char *e = getenv("GA_PRE_VIEWS"); const int v = e ? atoi(e) : kPreViews; return v < 1 ? 1 : v; }();
-    static const int nt = [] { const char *e = getenv("GA_PRE_NT"); return e ? atoi(e) : 0; }();
+    static const int nt = [] { const char *e = getenv("GA_PRE_NT"); return e ? atoi(e) : 0; }();   // (round 5's switch: non-temporal RECORD stores only)
+    const int pol = store_site(a.flags, GA_SURFEL_STORE_SITE_PRE), pol_rec = nt ? kStoreNT : pol;
     static const int spt = [] { const char *e = getenv("GA_PRE_SPLATS"); return e ? atoi(e) : kPreSplats; }();
     const bool lds = d.tiles <= kLdsTiles;
     const int vg = std::max(1, std::min(std::min(max_vg, d.V), lds ? kLdsTiles / d.tiles : max_vg));
     const int per = spt >= 4 ? 4 : (spt >= 2 ? 2 : 1);
     const dim3 grid((unsigned)((d.N + 256 * per - 1) / (256 * per)), (unsigned)((d.V + vg - 1) / vg));
 #define GA_PRE_LAUNCH(L, S)                                                                                                         \
-    hipLaunchKernelGGL((surfel_preprocess_kernel<L, S>), grid, dim3(256), (L) ? (size_t)vg * d.tiles * sizeof(uint32_t) : 0, s,       \
-                       a.means3D, a.opacities, a.colors, a.scales, a.rotations, a.viewmatrix, a.projmatrix, a.scale_modifier, d, vg, nt, \
+    do { if ((pol | pol_rec) != kStorePlain) GA_PRE_LAUNCH_P(L, S, true); else GA_PRE_LAUNCH_P(L, S, false); } while (0)
+#define GA_PRE_LAUNCH_P(L, S, P)                                                                                                    \
+    hipLaunchKernelGGL((surfel_preprocess_kernel<L, S, P>), grid, dim3(256), (L) ? (size_t)vg * d.tiles * sizeof(uint32_t) : 0, s,       \
+                       a.means3D, a.opacities, a.colors, a.scales, a.rotations, a.viewmatrix, a.projmatrix, a.scale_modifier, d, vg, pol, pol_rec, \
                        a.radii, ws.rect, ws.depth, ws.record, ws.tile_count, ws.view_total)
     if (lds) {
         if (per == 4) GA_PRE_LAUNCH(true, 4); else if (per == 2) GA_PRE_LAUNCH(true, 2); else GA_PRE_LAUNCH(true, 1);
@@ -293,6 +294,7 @@ void launch_preprocess(const GaSurfelForwardArgs &a, const Dims &d, const Worksp
         if (per == 4) GA_PRE_LAUNCH(false, 4); else if (per == 2) GA_PRE_LAUNCH(false, 2); else GA_PRE_LAUNCH(false, 1);
     }
 #undef GA_PRE_LAUNCH
+#undef GA_PRE_LAUNCH_P
 }
 
 }  // namespace ga

@@ -33,6 +33,7 @@ extern "C" {
 #define GA_ERR_BAD_SHAPE (-2)      /* N, V, H, W or capacity out of range (H, W <= 4096*16, V*tiles < 2^24) */
 #define GA_ERR_WORKSPACE (-3)      /* workspace_bytes smaller than ga_surfel_workspace_layout() says */
 #define GA_ERR_LAUNCH (-4)         /* a HIP launch failed (hipGetLastError is left set)            */
+#define GA_ERR_BAD_FLAGS (-5)      /* a store-policy field of `flags` (or of the GA_SURFEL_STORE override) holds the undefined value 3 */
 
 /* status words written by the device (int64 each) */
 #define GA_STATUS_NUM_RENDERED 0   /* D = sum over views of tiles touched (upstream `num_rendered`) */
@@ -109,6 +110,35 @@ typedef struct GaSurfelForwardArgs {
                                          56 MB of stores) are written by the blend launch's own workgroups as in rounds 1-5; default: by the
                                          otherwise idle waves of the per-tile sort launch in front of it, whose lists those tiles do not have */
 
+/* Cache policy of the forward's global STORES, per launch ("site"): bits 4..11 of `flags`, two bits per site.  Every launch of the
+ * forward is a large writer and the next launch depends on it; the policy only says how its bytes leave the CU -- results are
+ * bit-identical under every combination (tests/test_surfel_store_policy_gpu.py).
+ *   0 plain          write-back: the line stays dirty in the XCD's L2 until it is evicted or the launch ends
+ *   1 write-through  agent scope (sc1): the bytes leave for memory while the launch runs, nothing of them is dirty at its end
+ *   2 non-temporal   (nt) streaming hint
+ *   3                undefined: ga_surfel_forward returns GA_ERR_BAD_FLAGS
+ * Sites: PRE   preprocess: blend records, rect, depth, radii
+ *        FILL  tile scan + fill: keys, schedule (tile_order), tile_start, run table
+ *        SORT  per-tile sort: point_list and the background pixels of the empty tiles; non-temporal applies to the background pixels
+ *              only (nothing on the device reads them), point_list -- gathered by the blend right behind -- then stays plain
+ *        BLEND output pixels (also those a segmented tile's last workgroup writes) and seg_T
+ * The epoch-tagged exchange words of the segmented blend, the accumulating words of the workspace head and every load are not
+ * covered.  All sites plain is the measured choice (profiles/store_policy_ab.txt).  The environment variable
+ * GA_SURFEL_STORE = four digits "PFSB" (e.g. 0120), read once, replaces the field of every forward: an A/B aid. */
+#define GA_SURFEL_STORE_PLAIN 0
+#define GA_SURFEL_STORE_WRITE_THROUGH 1
+#define GA_SURFEL_STORE_NONTEMPORAL 2
+#define GA_SURFEL_STORE_SHIFT 4
+#define GA_SURFEL_STORE_MASK (0xFF << GA_SURFEL_STORE_SHIFT)
+#define GA_SURFEL_STORE_SITE_PRE 0
+#define GA_SURFEL_STORE_SITE_FILL 1
+#define GA_SURFEL_STORE_SITE_SORT 2
+#define GA_SURFEL_STORE_SITE_BLEND 3
+#define GA_SURFEL_STORE_SITES 4
+#define GA_SURFEL_STORE_FLAGS(pre, fill, sort, blend) \
+    ((((pre) & 3) | (((fill) & 3) << 2) | (((sort) & 3) << 4) | (((blend) & 3) << 6)) << GA_SURFEL_STORE_SHIFT)
+#define GA_SURFEL_STORE_DEFAULT GA_SURFEL_STORE_FLAGS(0, 0, 0, 0)   /* the measured choice */
+
 /* Byte offsets of the workspace sections (all 256-byte aligned).  Tests read the integer artefacts
  * (rect, tile ranges, sorted point list) straight out of the workspace through these offsets. */
 typedef struct GaSurfelWorkspaceLayout {
@@ -151,6 +181,10 @@ int ga_surfel_workspace_layout2(int32_t num_points, int32_t num_views, int32_t i
 /* host: enqueue the whole forward (preprocess, tile binning, per-tile depth sort, blend) on `stream`
  * (a hipStream_t passed as void* so that this header needs no HIP include). */
 int ga_surfel_forward(const GaSurfelForwardArgs *args, void *stream);
+
+/* host: the per-site store policies `flags` selects (policy[GA_SURFEL_STORE_SITE_*], the GA_SURFEL_STORE override NOT applied);
+ * GA_OK, GA_ERR_NULL_ARG, or GA_ERR_BAD_FLAGS when a site holds the undefined value 3 (policy[] is then left untouched) */
+int ga_surfel_store_policy(int32_t flags, int32_t policy[GA_SURFEL_STORE_SITES]);
 
 /* host: the per-pixel post-processing of GaussianRenderer2DGS.render (/root/reference/nsr/gs_surfel.py:121-163) over the
  * outputs of ga_surfel_forward, all views in one pass:

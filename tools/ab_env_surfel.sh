@@ -1,6 +1,7 @@
 #!/bin/bash
 # same-box A/B of an environment switch on the rasterizer forward (BASELINE configs[1] + the stress scene), alternating, three rounds.
 # usage (GPU box): bash tools/ab_env_surfel.sh GA_SURFEL_FLAGS=8 GA_SURFEL_FLAGS=0
+#                  bash tools/ab_env_surfel.sh GA_SURFEL_STORE=0000 GA_SURFEL_STORE=1010   (store policies, digits P F S B: include/ga_surfel.h)
 R=${GRAFT_REPO_ROOT:-/root/repo}
 for r in 1 2 3; do
   for kv in "$@"; do
