@@ -125,14 +125,30 @@ class GaKnnBackwardArgs(ctypes.Structure):
                 ("grad_query", ctypes.c_void_p), ("grad_target", ctypes.c_void_p)]
 
 
+class GaPhotoLossArgs(ctypes.Structure):
+    """include/ga_loss.h: GaPhotoLossArgs"""
+    _fields_ = [("num_images", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32), ("img1", ctypes.c_void_p), ("img2", ctypes.c_void_p),
+                ("out", ctypes.c_void_p), ("ssim_map", ctypes.c_void_p), ("grad_out", ctypes.c_void_p), ("grad_img1", ctypes.c_void_p),
+                ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class GaPhotoLossPlan(ctypes.Structure):
+    """include/ga_loss.h: GaPhotoLossPlan"""
+    _fields_ = [("tile_w", ctypes.c_int32), ("tile_h", ctypes.c_int32), ("threads", ctypes.c_int32), ("tiles_x", ctypes.c_int32),
+                ("tiles_y", ctypes.c_int32), ("lds_bytes", ctypes.c_int32), ("grid_x", ctypes.c_int64), ("num_partials", ctypes.c_int64)]
+
+
 GA_FPS_VARIANT_REGISTER, GA_FPS_VARIANT_STREAMING = 0, 1
+GA_PHOTO_LOSS_SAVE = 1
 GA_PC_KNN_MAX_K = 32
 
 EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspace_layout2", "ga_surfel_forward", "ga_surfel_postprocess",
            "ga_surfel_backward", "ga_surfel_backward_scratch_bytes", "ga_surfel_store_policy",
            "ga_tsdf_integrate", "ga_tsdf_mesh_scratch_bytes", "ga_tsdf_mesh_count", "ga_tsdf_mesh_emit", "ga_mesh_write_obj", "ga_mesh_cluster_labels",
            "ga_pc_fps", "ga_pc_fps_plan", "ga_pc_fps_workspace_bytes", "ga_pc_nearest",
-           "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward")
+           "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward",
+           "ga_photo_loss_plan", "ga_photo_loss_workspace_bytes", "ga_photo_loss_forward", "ga_photo_loss_backward")
 
 _lib = None
 
@@ -204,6 +220,14 @@ def lib():
         L.ga_pc_knn_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GaKnnPlan)]
         L.ga_pc_knn_backward.restype = ctypes.c_int
         L.ga_pc_knn_backward.argtypes = [ctypes.POINTER(GaKnnBackwardArgs), ctypes.c_void_p]
+        L.ga_photo_loss_plan.restype = ctypes.c_int
+        L.ga_photo_loss_plan.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(GaPhotoLossPlan)]
+        L.ga_photo_loss_workspace_bytes.restype = ctypes.c_size_t
+        L.ga_photo_loss_workspace_bytes.argtypes = [ctypes.c_int32] * 5
+        L.ga_photo_loss_forward.restype = ctypes.c_int
+        L.ga_photo_loss_forward.argtypes = [ctypes.POINTER(GaPhotoLossArgs), ctypes.c_void_p]
+        L.ga_photo_loss_backward.restype = ctypes.c_int
+        L.ga_photo_loss_backward.argtypes = [ctypes.POINTER(GaPhotoLossArgs), ctypes.c_void_p]
         _lib = L
     return _lib
 
