@@ -139,8 +139,26 @@ class GaPhotoLossPlan(ctypes.Structure):
                 ("tiles_y", ctypes.c_int32), ("lds_bytes", ctypes.c_int32), ("grid_x", ctypes.c_int64), ("num_partials", ctypes.c_int64)]
 
 
+class GaGeoLossArgs(ctypes.Structure):
+    """include/ga_loss.h: GaGeoLossArgs"""
+    _fields_ = [("num_views", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("flags", ctypes.c_int32),
+                ("tanfov", ctypes.c_double), ("view", ctypes.c_void_p), ("rend_normal", ctypes.c_void_p), ("depth", ctypes.c_void_p),
+                ("alpha", ctypes.c_void_p), ("dist", ctypes.c_void_p), ("target_normal", ctypes.c_void_p), ("mask", ctypes.c_void_p),
+                ("out", ctypes.c_void_p), ("surf_normal_out", ctypes.c_void_p), ("grad_out", ctypes.c_void_p),
+                ("grad_rend_normal", ctypes.c_void_p), ("grad_depth", ctypes.c_void_p), ("grad_dist", ctypes.c_void_p),
+                ("grad_alpha", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
+
+class GaGeoLossPlan(ctypes.Structure):
+    """include/ga_loss.h: GaGeoLossPlan"""
+    _fields_ = [("tile_w", ctypes.c_int32), ("tile_h", ctypes.c_int32), ("threads", ctypes.c_int32), ("tiles_x", ctypes.c_int32),
+                ("tiles_y", ctypes.c_int32), ("lds_bytes", ctypes.c_int32), ("lds_bytes_backward", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("grid_x", ctypes.c_int64), ("num_partials", ctypes.c_int64)]
+
+
 GA_FPS_VARIANT_REGISTER, GA_FPS_VARIANT_STREAMING = 0, 1
 GA_PHOTO_LOSS_SAVE = 1
+GA_GEO_LOSS_TARGET, GA_GEO_LOSS_NORMALS = 1, 2
 GA_PC_KNN_MAX_K = 32
 
 EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspace_layout2", "ga_surfel_forward", "ga_surfel_postprocess",
@@ -148,7 +166,8 @@ EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspa
            "ga_tsdf_integrate", "ga_tsdf_mesh_scratch_bytes", "ga_tsdf_mesh_count", "ga_tsdf_mesh_emit", "ga_mesh_write_obj", "ga_mesh_cluster_labels",
            "ga_pc_fps", "ga_pc_fps_plan", "ga_pc_fps_workspace_bytes", "ga_pc_nearest",
            "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward",
-           "ga_photo_loss_plan", "ga_photo_loss_workspace_bytes", "ga_photo_loss_forward", "ga_photo_loss_backward")
+           "ga_photo_loss_plan", "ga_photo_loss_workspace_bytes", "ga_photo_loss_forward", "ga_photo_loss_backward",
+           "ga_geo_loss_plan", "ga_geo_loss_workspace_bytes", "ga_geo_loss_forward", "ga_geo_loss_backward")
 
 _lib = None
 
@@ -228,6 +247,14 @@ def lib():
         L.ga_photo_loss_forward.argtypes = [ctypes.POINTER(GaPhotoLossArgs), ctypes.c_void_p]
         L.ga_photo_loss_backward.restype = ctypes.c_int
         L.ga_photo_loss_backward.argtypes = [ctypes.POINTER(GaPhotoLossArgs), ctypes.c_void_p]
+        L.ga_geo_loss_plan.restype = ctypes.c_int
+        L.ga_geo_loss_plan.argtypes = [ctypes.c_int32] * 3 + [ctypes.POINTER(GaGeoLossPlan)]
+        L.ga_geo_loss_workspace_bytes.restype = ctypes.c_size_t
+        L.ga_geo_loss_workspace_bytes.argtypes = [ctypes.c_int32] * 3
+        L.ga_geo_loss_forward.restype = ctypes.c_int
+        L.ga_geo_loss_forward.argtypes = [ctypes.POINTER(GaGeoLossArgs), ctypes.c_void_p]
+        L.ga_geo_loss_backward.restype = ctypes.c_int
+        L.ga_geo_loss_backward.argtypes = [ctypes.POINTER(GaGeoLossArgs), ctypes.c_void_p]
         _lib = L
     return _lib
 

@@ -23,9 +23,10 @@ constexpr int kHalo = kTile + kTaps - 1;  // 42
 constexpr int kHaloStride = kHalo + 1;    // 43: see 'LDS images'
 constexpr int kThreads = 256;
 constexpr int kRowItems = kHalo * (kTile / 4);   // row pass: (halo row, group of 4 columns)
-constexpr int kReduceThreads = 256;
 constexpr float kC1 = 0.01f * 0.01f;
 constexpr float kC2 = 0.03f * 0.03f;
+
+#include "loss_reduce.h"   // block_sum3, loss_reduce_kernel (shared with geo_loss.hip)
 
 struct Window {
     float w[kTaps];
@@ -93,29 +94,6 @@ __device__ __forceinline__ void column_pass(const float *rowbuf, int px, int py0
 #pragma unroll
         for (int k = 0; k < kTaps; ++k) a = fmaf(win.w[k], v[j + k], a);
         out[j] = a;
-    }
-}
-
-// fixed-order sum of three doubles per lane over the workgroup; the result is valid in thread 0
-__device__ __forceinline__ void block_sum3(double v[3], double *red /* [3][waves] */) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off, 64);
-    }
-    const int wave = threadIdx.x >> 6, waves = kThreads / 64;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) red[q * waves + wave] = v[q];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            double s = red[q * waves];
-            for (int w = 1; w < waves; ++w) s += red[q * waves + w];
-            v[q] = s;
-        }
     }
 }
 
@@ -230,32 +208,6 @@ __global__ __launch_bounds__(kThreads) void photo_loss_forward_kernel(const floa
         p[1] = (float)v[1];
         p[2] = (float)v[2];
     }
-}
-
-// one workgroup per image: its partials are contiguous ([C * tiles] x 3); fixed order: lane-strided, then a tree
-__global__ __launch_bounds__(kReduceThreads) void photo_loss_reduce_kernel(const float *__restrict__ partials, float *__restrict__ out,
-                                                                           int per_image, double inv_count) {
-    __shared__ double red[3][kReduceThreads];
-    const float *p = partials + (size_t)blockIdx.x * (size_t)per_image * 3;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    for (int i = threadIdx.x; i < per_image; i += kReduceThreads) {
-        s0 += (double)p[(size_t)i * 3 + 0];
-        s1 += (double)p[(size_t)i * 3 + 1];
-        s2 += (double)p[(size_t)i * 3 + 2];
-    }
-    red[0][threadIdx.x] = s0;
-    red[1][threadIdx.x] = s1;
-    red[2][threadIdx.x] = s2;
-    __syncthreads();
-    for (int off = kReduceThreads / 2; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) {
-            red[0][threadIdx.x] += red[0][threadIdx.x + off];
-            red[1][threadIdx.x] += red[1][threadIdx.x + off];
-            red[2][threadIdx.x] += red[2][threadIdx.x + off];
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < 3) out[(size_t)blockIdx.x * 3 + threadIdx.x] = (float)(red[threadIdx.x][0] * inv_count);
 }
 
 __global__ __launch_bounds__(kThreads) void photo_loss_backward_kernel(const float *__restrict__ img1, const float *__restrict__ img2,
@@ -380,7 +332,7 @@ extern "C" int ga_photo_loss_forward(const GaPhotoLossArgs *a, void *stream_v) {
                            partials, (float *)nullptr, (float *)nullptr, (float *)nullptr, a->channels, a->height, a->width, pl.tiles_x,
                            pl.tiles_y, win);
     const int per_image = a->channels * pl.tiles_x * pl.tiles_y;
-    hipLaunchKernelGGL(photo_loss_reduce_kernel, dim3((unsigned)a->num_images), dim3(kReduceThreads), 0, s, partials, a->out, per_image,
+    hipLaunchKernelGGL(loss_reduce_kernel, dim3((unsigned)a->num_images), dim3(kReduceThreads), 0, s, partials, a->out, per_image,
                        1.0 / ((double)a->channels * a->height * a->width));
     return hipGetLastError() == hipSuccess ? GA_OK : GA_ERR_LAUNCH;
 }
