@@ -156,6 +156,42 @@ class GaGeoLossPlan(ctypes.Structure):
                 ("reserved", ctypes.c_int32), ("grid_x", ctypes.c_int64), ("num_partials", ctypes.c_int64)]
 
 
+class GaFitPlan(ctypes.Structure):
+    """include/ga_fit.h: GaFitPlan"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("threads", "pack_vec", "grid_activate", "grid_adam", "grid_pack_x", "grid_pack_y")] + \
+               [(n, ctypes.c_size_t) for n in ("means", "opacities", "colors", "scales", "rotations", "inv_norm", "workspace_bytes")]
+
+
+class GaFitActivateArgs(ctypes.Structure):
+    """include/ga_fit.h: GaFitActivateArgs"""
+    _fields_ = [("num_points", ctypes.c_int32), ("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("raw", "means", "opacities", "colors", "scales", "rotations", "inv_norm")]
+
+
+class GaFitPackArgs(ctypes.Structure):
+    """include/ga_fit.h: GaFitPackArgs"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("num_views", "height", "width", "reserved")] + \
+               [(n, ctypes.c_void_p) for n in ("color", "allmap", "view", "g_image", "g_rend_normal", "g_depth", "g_dist", "g_alpha",
+                                               "g_color", "g_allmap")]
+
+
+class GaFitAdamArgs(ctypes.Structure):
+    """include/ga_fit.h: GaFitAdamArgs"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("num_points", "num_views", "flags", "max_steps")] + \
+               [(n, ctypes.c_void_p) for n in ("g_means", "g_opacities", "g_colors", "g_scales", "g_rotations", "opacities", "colors",
+                                               "scales", "rotations", "inv_norm", "raw", "m", "v", "radii", "table", "counter")] + \
+               [(n, ctypes.c_float) for n in ("beta1", "one_minus_beta1", "beta2", "one_minus_beta2", "eps")] + \
+               [("reserved", ctypes.c_int32), ("raw_grad", ctypes.c_void_p)]
+
+
+class GaFitAdvanceArgs(ctypes.Structure):
+    """include/ga_fit.h: GaFitAdvanceArgs"""
+    _fields_ = [("num_views", ctypes.c_int32), ("max_steps", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("counter", "photo_out", "geo_out", "w_photo", "w_geo", "history")] + \
+               [("ssim_bias", ctypes.c_float), ("reserved", ctypes.c_int32), ("status", ctypes.c_void_p), ("seen", ctypes.c_void_p)]
+
+
+GA_FIT_PARAMS, GA_FIT_GROUPS, GA_FIT_TABLE_COLS, GA_FIT_HISTORY_COLS, GA_FIT_VISIBLE_ONLY = 13, 5, 8, 8, 1
 GA_FPS_VARIANT_REGISTER, GA_FPS_VARIANT_STREAMING = 0, 1
 GA_PHOTO_LOSS_SAVE = 1
 GA_GEO_LOSS_TARGET, GA_GEO_LOSS_NORMALS = 1, 2
@@ -167,7 +203,8 @@ EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspa
            "ga_pc_fps", "ga_pc_fps_plan", "ga_pc_fps_workspace_bytes", "ga_pc_nearest",
            "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward",
            "ga_photo_loss_plan", "ga_photo_loss_workspace_bytes", "ga_photo_loss_forward", "ga_photo_loss_backward",
-           "ga_geo_loss_plan", "ga_geo_loss_workspace_bytes", "ga_geo_loss_forward", "ga_geo_loss_backward")
+           "ga_geo_loss_plan", "ga_geo_loss_workspace_bytes", "ga_geo_loss_forward", "ga_geo_loss_backward",
+           "ga_fit_plan", "ga_fit_activate", "ga_fit_pack_grads", "ga_fit_adam", "ga_fit_advance")
 
 _lib = None
 
@@ -255,6 +292,12 @@ def lib():
         L.ga_geo_loss_forward.argtypes = [ctypes.POINTER(GaGeoLossArgs), ctypes.c_void_p]
         L.ga_geo_loss_backward.restype = ctypes.c_int
         L.ga_geo_loss_backward.argtypes = [ctypes.POINTER(GaGeoLossArgs), ctypes.c_void_p]
+        L.ga_fit_plan.restype = ctypes.c_int
+        L.ga_fit_plan.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(GaFitPlan)]
+        for name, struct in (("ga_fit_activate", GaFitActivateArgs), ("ga_fit_pack_grads", GaFitPackArgs), ("ga_fit_adam", GaFitAdamArgs),
+                             ("ga_fit_advance", GaFitAdvanceArgs)):
+            getattr(L, name).restype = ctypes.c_int
+            getattr(L, name).argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
         _lib = L
     return _lib
 
