@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .diff_surfel_rasterization import EXTRA_FLAGS, SurfelWorkspace, _seg_T, default_capacity
+from .diff_surfel_rasterization import SurfelForwardPlan, SurfelWorkspace, default_capacity
 
 GROUPS = ("xyz", "opacity", "scale", "rotation", "rgb")
 COLUMNS = {"xyz": (0, 3), "opacity": (3, 4), "scale": (4, 6), "rotation": (6, 10), "rgb": (10, 13)}
@@ -198,7 +198,10 @@ class SurfelFitter:
                 raise ValueError(f"views of {H} x {W} are out of the loss kernels' range")
             self._photo_ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
             self._geo_ws = torch.zeros(gbytes, dtype=torch.uint8, device=dev)
-            self._ws = SurfelWorkspace(dev, N, V, H, W, int(capacity) if capacity is not None else default_capacity(N, V))
+            ws = SurfelWorkspace(dev, N, V, H, W, int(capacity) if capacity is not None else default_capacity(N, V))
+            self._fwd = SurfelForwardPlan._bound((self._means, self._opac, self._colors, self._scales, self._rots, self._view, self._proj,
+                                                  self._bg), H, W, 1.0, ws, for_backward=True,
+                                                 outputs=(self._color, self._allmap, self._radii))
             self._steps = self._snap_steps = 0
             self._graph = None
             self._side = torch.cuda.Stream(dev)
@@ -240,17 +243,12 @@ class SurfelFitter:
 
     # ---- the launches ------------------------------------------------------------------------------------------------------------
     def _bind(self):
-        """(re)build every argument block: after construction and after the workspace has grown"""
-        N, V, H, W, ws = self.N, self.V, self.H, self.W, self._ws
-        seg_T = _seg_T(ws)
+        """(re)build every argument block but the forward's (``self._fwd`` holds it): after construction and after the workspace has
+        grown"""
+        N, V, H, W, ws = self.N, self.V, self.H, self.W, self._fwd.ws
         self._a_act = _lib.GaFitActivateArgs(N, 0, self._raw.data_ptr(), self._means.data_ptr(), self._opac.data_ptr(),
                                              self._colors.data_ptr(), self._scales.data_ptr(), self._rots.data_ptr(),
                                              self._inv_norm.data_ptr())
-        self._a_fwd = _lib.GaSurfelForwardArgs(
-            N, V, H, W, 1.0, ws.clean_flag() | EXTRA_FLAGS, self._means.data_ptr(), self._opac.data_ptr(), self._colors.data_ptr(),
-            self._scales.data_ptr(), self._rots.data_ptr(), self._view.data_ptr(), self._proj.data_ptr(), self._bg.data_ptr(),
-            self._color.data_ptr(), self._allmap.data_ptr(), self._radii.data_ptr(), ws.ptr, ws.layout.total_bytes, ws.capacity,
-            None, ws.seg_capacity, _ptr(seg_T), seg_T.numel() if seg_T is not None else 0)
         self._a_post = _lib.GaSurfelPostArgs(V, H, W, self._color.data_ptr(), self._allmap.data_ptr(), self._view.data_ptr(),
                                              self._image.data_ptr(), self._rend_normal.data_ptr(), self._depth.data_ptr())
         self._a_photo = _lib.GaPhotoLossArgs(V, 3, H, W, _lib.GA_PHOTO_LOSS_SAVE, 0, self._image.data_ptr(), self._targets.data_ptr(),
@@ -270,13 +268,12 @@ class SurfelFitter:
                                           self._g_image.data_ptr(), self._g_rend_normal.data_ptr(), self._g_depth.data_ptr(),
                                           self._g_dist.data_ptr(), self._g_alpha.data_ptr(), self._g_color.data_ptr(),
                                           self._g_allmap.data_ptr())
-        nbytes = int(self._L.ga_surfel_backward_scratch_bytes(ctypes.byref(self._a_fwd)))
+        fwd = self._fwd.backward_args()
+        nbytes = int(self._L.ga_surfel_backward_scratch_bytes(ctypes.byref(fwd)))
         if nbytes == 0:
             raise RuntimeError("ga_surfel_backward_scratch_bytes: bad shape")
         if getattr(self, "_scratch", None) is None or self._scratch.numel() < nbytes:
             self._scratch = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        fwd = _lib.GaSurfelForwardArgs.from_buffer_copy(self._a_fwd)
-        fwd.flags = 0
         self._a_bwd = _lib.GaSurfelBackwardArgs(fwd, self._g_color.data_ptr(), self._g_allmap.data_ptr(), self._scratch.data_ptr(),
                                                 self._scratch.numel(), self._g_means.data_ptr(), self._g_opac.data_ptr(),
                                                 self._g_colors.data_ptr(), self._g_scales.data_ptr(), self._g_rots.data_ptr())
@@ -297,10 +294,7 @@ class SurfelFitter:
         L, ref = self._L, ctypes.byref
         s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         _lib.check(L.ga_fit_activate(ref(self._a_act), s), "ga_fit_activate")
-        _lib.check(L.ga_surfel_forward(ref(self._a_fwd), s), "ga_surfel_forward")
-        if not self._ws.clean_flag():        # from the second forward on a workspace the clearing memset is not needed any more
-            self._ws.clean = True
-            self._a_fwd.flags |= _lib.GA_SURFEL_FLAG_WORKSPACE_CLEAN
+        self._fwd.run()
         _lib.check(L.ga_surfel_postprocess(ref(self._a_post), s), "ga_surfel_postprocess")
         self._alpha.copy_(self._allmap[:, 1:2])      # the loss kernels read contiguous [V,1,H,W] maps: two strided copies
         self._dist.copy_(self._allmap[:, 6:7])
@@ -349,10 +343,8 @@ class SurfelFitter:
             main.wait_stream(self._side)
 
     def _grow(self, seen):
-        st = torch.zeros(_lib.GA_STATUS_WORDS, dtype=torch.int64)
-        st[_lib.GA_STATUS_NUM_RENDERED], st[_lib.GA_STATUS_SEG_WORK] = int(seen[1]), int(seen[2])
         self._graph = None
-        self._ws = self._ws.grown(st)
+        self._fwd.rebind(self._fwd.ws.grown(need=int(seen[1]), seg_need=int(seen[2])))
         self._bind()
 
     # ---- the public surface ------------------------------------------------------------------------------------------------------
@@ -399,11 +391,11 @@ class SurfelFitter:
     @property
     def capacity(self) -> int:
         """binned (tile, surfel) entries the rasterizer workspace holds at present"""
-        return self._ws.capacity
+        return self._fwd.ws.capacity
 
     def entries(self) -> int:
         """binned (tile, surfel) entries of the last forward (one read-back)"""
-        return int(self._ws.status()[_lib.GA_STATUS_NUM_RENDERED].cpu())
+        return int(self._fwd.ws.status()[_lib.GA_STATUS_NUM_RENDERED].cpu())
 
     def state_dict(self) -> dict:
         """copies of raw, m, v and the loss history, and the number of steps taken: what ``load_state_dict`` of a fitter of the same N

@@ -13,7 +13,7 @@ import os
 import torch
 
 from . import io_formats
-from .diff_surfel_rasterization import _get_workspace, postprocess_views, rasterize_views
+from .diff_surfel_rasterization import SurfelForwardPlan, cached_workspace, postprocess_views, rasterize_views
 from . import _lib
 
 
@@ -53,32 +53,31 @@ class GaussianRenderer2DGS:
                 outs["depth"].append(torch.nan_to_num(allmap[:, 5:6], 0, 0))
                 outs["dist"].append(allmap[:, 6:7])
             return {k: torch.stack(v, dim=0) for k, v in outs.items()}
-        return self._render_nograd(gaussians, cam_view, cam_view_proj, bg_color, scale_modifier, S, True)[0]
+        return self._render_nograd(gaussians, cam_view, cam_view_proj, bg_color, scale_modifier, S)
 
-    def _render_nograd(self, gaussians, cam_view, cam_view_proj, bg_color, scale_modifier, S, check_overflow):
+    def _render_nograd(self, gaussians, cam_view, cam_view_proj, bg_color, scale_modifier, S, rasterize=None):
         """The inference branch of ``render``: per batch item one rasterizer call for all V views and one fused post-processing
-        pass.  Returns (dict, workspaces used): with ``check_overflow=False`` nothing synchronises and the caller reads the
-        workspaces' status words itself (``render_levels``)."""
+        pass.  ``rasterize``: called as ``rasterize_views`` and in its place (``render_levels``: a forward that does not
+        synchronise)."""
         B, V = cam_view.shape[:2]
         dev = gaussians.device
         image = torch.empty((B, V, 3, S, S), dtype=torch.float32, device=dev)
         rend_normal = torch.empty((B, V, 3, S, S), dtype=torch.float32, device=dev)
         depth = torch.empty((B, V, 1, S, S), dtype=torch.float32, device=dev)
-        allmaps, used = [], []
+        allmaps = []
         for b in range(B):
             g = gaussians[b]
             view = cam_view[b].float()
-            color, _radii, allmap, ws = rasterize_views(
+            color, _radii, allmap, _ = (rasterize or rasterize_views)(
                 g[:, 0:3], g[:, 3:4], g[:, 10:13], g[:, 4:6], g[:, 6:10], view, cam_view_proj[b].float(),
-                bg_color.to(g.device), S, S, scale_modifier, check_overflow=check_overflow)
+                bg_color.to(g.device), S, S, scale_modifier)
             # clamp of the image (:163), view -> world rotation of the normals (:126-128), NaN scrubbing of the median depth
             # (:133-134, depth_ratio = 1) -- one fused pass written straight into the stacked outputs
             postprocess_views(color, allmap, view, image[b], rend_normal[b], depth[b])
             allmaps.append(allmap)
-            used.append(ws)
         # alpha / dist are channels 1 / 6 of allmap (:121,142): views for one batch item, one stack otherwise
         am = allmaps[0].unsqueeze(0) if B == 1 else torch.stack(allmaps, dim=0)
-        return {"image": image, "alpha": am[:, :, 1:2], "depth": depth, "rend_normal": rend_normal, "dist": am[:, :, 6:7]}, used
+        return {"image": image, "alpha": am[:, :, 1:2], "depth": depth, "rend_normal": rend_normal, "dist": am[:, :, 6:7]}
 
     @torch.no_grad()
     def render_levels(self, gaussian_sets, output_sizes, cam_view, cam_view_proj, cam_pos, tanfov, bg_color=None, scale_modifier=1):
@@ -87,8 +86,9 @@ class GaussianRenderer2DGS:
         ``[render(g, ..., output_size=s) for g, s in zip(gaussian_sets, output_sizes)]`` would, but overlapped: set k runs on side
         stream k % 2, so the latency-bound front-end (preprocess / binning / sort) of one set hides under the issue-bound blend of
         its neighbour (two independent forwards on two streams: +11 %, profiles/r5_overlap_probe.txt), and the overflow words of
-        all sets are read back ONCE after the last launch instead of one host synchronisation per set.  A set whose workspace
-        overflowed (first use of a shape with unusually long lists) is rendered again the ordinary way."""
+        all sets -- each set's own: the workspace's, or a copy where a later set reuses the workspace -- are read back ONCE after the
+        last launch instead of one host synchronisation per set.  A set whose workspace overflowed (first use of a shape with
+        unusually long lists) is rendered again the ordinary way."""
         if bg_color is None:
             bg_color = self.bg_color
         sets = [g.contiguous().float() for g in gaussian_sets]
@@ -100,32 +100,37 @@ class GaussianRenderer2DGS:
         main = torch.cuda.current_stream(dev)
         if getattr(self, "_side", None) is None or self._side[0].device != dev:
             self._side = (torch.cuda.Stream(dev), torch.cuda.Stream(dev))
-        B, V = cam_view.shape[:2]
-        lane_of = {}
-        for k, (g, S) in enumerate(zip(sets, output_sizes)):        # workspaces are long-lived: created on the caller's stream; two sets
-            _get_workspace(dev, g.shape[1], V, S, S)                 # of one shape share a workspace and therefore a stream
-            lane_of.setdefault((g.shape[1], S), k % 2)
+        V = cam_view.shape[1]
+        shapes = [(g.shape[1], S) for g, S in zip(sets, output_sizes)]
+        lanes = {}
+        for k, (n, S) in enumerate(shapes):                          # workspaces are long-lived: created on the caller's stream; two sets
+            if (n, S) not in lanes:                                  # of one shape share a workspace and therefore a stream
+                lanes[(n, S)] = (cached_workspace(dev, n, V, S, S), self._side[k % 2])
         fork = torch.cuda.Event()
         fork.record(main)
-        results = []
-        for g, S in zip(sets, output_sizes):
-            st = self._side[lane_of[(g.shape[1], S)]]
-            st.wait_event(fork)
-            with torch.cuda.stream(st):
-                res, used = self._render_nograd(g, cam_view, cam_view_proj, bg_color, scale_modifier, S, False)
+        results, words = [], []
+        for k, (g, S) in enumerate(zip(sets, output_sizes)):
+            ws, side = lanes[shapes[k]]
+
+            def enqueue(*args):
+                plan = SurfelForwardPlan(*args, workspace=ws)
+                plan.run()
+                # the status words belong to the LAST forward on a workspace: a later set of this shape overwrites them, so this set
+                # keeps a copy (same stream, hence taken before that forward); a set alone on its workspace enqueues nothing more
+                words.append(ws.status()[:4].clone() if shapes[k] in shapes[k + 1:] else ws.status()[:4])
+                return plan.color, plan.radii, plan.allmap, ws
+
+            side.wait_event(fork)
+            with torch.cuda.stream(side):
+                res = self._render_nograd(g, cam_view, cam_view_proj, bg_color, scale_modifier, S, enqueue)
             for t in (res["image"], res["rend_normal"], res["depth"], res["alpha"]):
                 t.record_stream(main)                                # (allocated on the side stream, consumed on the caller's)
-            results.append((res, used))
-        for st in self._side:
-            main.wait_stream(st)
-        words = torch.stack([ws.status()[:4] for _, used in results for ws in used]).cpu()       # the one synchronisation
-        at = 0
-        out = []
-        for (res, used), g, S in zip(results, sets, output_sizes):
-            bad = bool(words[at:at + len(used), _lib.GA_STATUS_OVERFLOW].any())
-            at += len(used)
-            out.append(self.render(g, cam_view, cam_view_proj, cam_pos, tanfov, bg_color, scale_modifier, S) if bad else res)
-        return out
+            results.append(res)
+        for side in self._side:
+            main.wait_stream(side)
+        words = torch.stack(words).cpu()                             # the one synchronisation; one row per set (one batch item each)
+        return [self.render(g, cam_view, cam_view_proj, cam_pos, tanfov, bg_color, scale_modifier, S) if int(st[_lib.GA_STATUS_OVERFLOW]) else res
+                for st, res, g, S in zip(words, results, sets, output_sizes)]
 
     def save_2dgs_ply(self, path, gaussians, compatible=True):
         """nsr/gs_surfel.py:206-265; the upstream body references undefined names -- ``io_formats.save_2dgs_ply`` writes the

@@ -446,7 +446,9 @@ def test_render_levels_overlapped_on_two_streams_equals_one_render_per_set(gpu_d
     """GaussianRenderer2DGS.render_levels (the four levels of triplane_decode, vit/vit_triplane.py:1550-1591): independent surfel
     sets on two side streams with ONE overflow read-back -- every tensor bit-identical to render() set by set; a set whose
     workspace overflows (splats much larger than the default capacity expects) is rendered again the ordinary way; repeated
-    calls (workspaces now 'clean') and two sets of one shape (one shared workspace, one stream) included."""
+    calls (workspaces now 'clean') and two sets of one shape (one shared workspace, one stream) included -- also where the set
+    that overflows shares its workspace with a later set that fits: that set's forward overwrites the workspace's status words,
+    and the overflow must be found all the same (both orders of the two)."""
     from gaussiananything_amd import diff_surfel_rasterization as dsr
     from gaussiananything_amd.gs_surfel import GaussianRenderer2DGS
     cams = synthetic.eval_cameras(6)
@@ -454,22 +456,25 @@ def test_render_levels_overlapped_on_two_streams_equals_one_render_per_set(gpu_d
     big = synthetic.random_surfels(2500, seed=9)
     big[0, :, 4:6] *= 12.0                                   # hundreds of tiles per splat: far beyond 2 N V entries
     sets = [synthetic.random_surfels(700, seed=5), synthetic.surface_surfels(9000, seed=6), big, synthetic.random_surfels(700, seed=7),
-            synthetic.surface_surfels(30000, seed=8)]
+            synthetic.surface_surfels(30000, seed=8), synthetic.random_surfels(2500, seed=10)]
     sets = [g.to(gpu_device) for g in sets]
-    sizes = [64, 128, 96, 64, 256]
+    sizes = [64, 128, 96, 64, 256, 96]
     r = GaussianRenderer2DGS(512, 3, {})
+    key = (str(gpu_device), 2500, 6, 96, 96)
     dsr._ws_cache.clear()
-    for rep in range(3):
-        if rep == 1:
+    r.render(sets[5], cv, cvp, cp, cams["tanfov"], output_size=96)      # the precondition: the last set alone fits the default capacity
+    assert dsr._ws_cache[key].capacity == dsr.default_capacity(2500, 6)
+    dsr._ws_cache.clear()
+    for rep, order in enumerate(([0, 1, 2, 3, 4, 5], [0, 1, 2, 3, 4, 5], [0, 1, 2, 3, 4, 5], [5, 2])):
+        if rep in (1, 3):
             dsr._ws_cache.clear()                            # the overflow is found again on fresh workspaces
-        got = r.render_levels(sets, sizes, cv, cvp, cp, cams["tanfov"])
+        got = r.render_levels([sets[i] for i in order], [sizes[i] for i in order], cv, cvp, cp, cams["tanfov"])
         torch.cuda.synchronize()
-        for g, S, res in zip(sets, sizes, got):
-            want = r.render(g, cv, cvp, cp, cams["tanfov"], output_size=S)
+        for i, res in zip(order, got):
+            want = r.render(sets[i], cv, cvp, cp, cams["tanfov"], output_size=sizes[i])
             assert set(res) == set(want)
             for k in want:
-                assert res[k].shape == want[k].shape and torch.equal(res[k], want[k]), (rep, S, k)
-    key = (str(gpu_device), 2500, 6, 96, 96)
+                assert res[k].shape == want[k].shape and torch.equal(res[k], want[k]), (rep, i, k)
     assert key in dsr._ws_cache and dsr._ws_cache[key].capacity > dsr.default_capacity(2500, 6)     # it did overflow and grow
 
 
