@@ -191,6 +191,29 @@ class GaFitAdvanceArgs(ctypes.Structure):
                [("ssim_bias", ctypes.c_float), ("reserved", ctypes.c_int32), ("status", ctypes.c_void_p), ("seen", ctypes.c_void_p)]
 
 
+class GaFitAccumulateArgs(ctypes.Structure):
+    """include/ga_densify.h: GaFitAccumulateArgs"""
+    _fields_ = [("num_points", ctypes.c_int32), ("num_views", ctypes.c_int32), ("tanfov", ctypes.c_float), ("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("g_means", "means", "radii", "view", "grad_accum", "denom", "max_radius")]
+
+
+class GaDensifyArgs(ctypes.Structure):
+    """include/ga_densify.h: GaDensifyArgs"""
+    _fields_ = [("num_points", ctypes.c_int32), ("flags", ctypes.c_int32), ("round", ctypes.c_uint32), ("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_float) for n in ("grad_threshold", "min_opacity", "percent_dense", "extent", "max_screen_size")] + \
+               [("reserved2", ctypes.c_int32), ("seed", ctypes.c_uint64)] + \
+               [(n, ctypes.c_void_p) for n in ("raw", "m", "v", "opacities", "scales", "rotations", "grad_accum", "denom", "max_radius",
+                                               "out_raw", "out_m", "out_v", "parent", "noise_out", "out_counts", "workspace")] + \
+               [("workspace_bytes", ctypes.c_size_t)]
+
+
+class GaFitResetOpacityArgs(ctypes.Structure):
+    """include/ga_densify.h: GaFitResetOpacityArgs"""
+    _fields_ = [("num_points", ctypes.c_int32), ("logit_cap", ctypes.c_float), ("raw", ctypes.c_void_p), ("m", ctypes.c_void_p),
+                ("v", ctypes.c_void_p)]
+
+
+GA_DENSIFY_PRUNE_ONLY, GA_DENSIFY_COUNTS = 1, 8
 GA_FIT_PARAMS, GA_FIT_GROUPS, GA_FIT_TABLE_COLS, GA_FIT_HISTORY_COLS, GA_FIT_VISIBLE_ONLY = 13, 5, 8, 8, 1
 GA_FPS_VARIANT_REGISTER, GA_FPS_VARIANT_STREAMING = 0, 1
 GA_PHOTO_LOSS_SAVE = 1
@@ -204,7 +227,8 @@ EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspa
            "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward",
            "ga_photo_loss_plan", "ga_photo_loss_workspace_bytes", "ga_photo_loss_forward", "ga_photo_loss_backward",
            "ga_geo_loss_plan", "ga_geo_loss_workspace_bytes", "ga_geo_loss_forward", "ga_geo_loss_backward",
-           "ga_fit_plan", "ga_fit_activate", "ga_fit_pack_grads", "ga_fit_adam", "ga_fit_advance")
+           "ga_fit_plan", "ga_fit_activate", "ga_fit_pack_grads", "ga_fit_adam", "ga_fit_advance",
+           "ga_fit_accumulate", "ga_densify_workspace_bytes", "ga_densify", "ga_fit_reset_opacity")
 
 _lib = None
 
@@ -295,9 +319,12 @@ def lib():
         L.ga_fit_plan.restype = ctypes.c_int
         L.ga_fit_plan.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(GaFitPlan)]
         for name, struct in (("ga_fit_activate", GaFitActivateArgs), ("ga_fit_pack_grads", GaFitPackArgs), ("ga_fit_adam", GaFitAdamArgs),
-                             ("ga_fit_advance", GaFitAdvanceArgs)):
+                             ("ga_fit_advance", GaFitAdvanceArgs), ("ga_fit_accumulate", GaFitAccumulateArgs),
+                             ("ga_densify", GaDensifyArgs), ("ga_fit_reset_opacity", GaFitResetOpacityArgs)):
             getattr(L, name).restype = ctypes.c_int
             getattr(L, name).argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]
+        L.ga_densify_workspace_bytes.restype = ctypes.c_size_t
+        L.ga_densify_workspace_bytes.argtypes = [ctypes.c_int32]
         _lib = L
     return _lib
 

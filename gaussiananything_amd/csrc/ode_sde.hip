@@ -26,36 +26,17 @@
 #include <stdint.h>
 
 #include "../../include/ga_dit.h"
+#include "philox.h"
 
 namespace gasde {
-
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4])
-{
-#pragma unroll
-    for (int round = 0; round < 10; ++round) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
 
 // the normal of draw index j at step `step` (ga_dit.h: "noise of ga_sde_step")
 __device__ __forceinline__ float normal_of(uint64_t seed, uint32_t step, uint32_t stream, int64_t j)
 {
     uint32_t w[4];
-    philox4x32_10((uint32_t)(j >> 2), step, stream, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+    gaphilox::philox4x32_10((uint32_t)(j >> 2), step, stream, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
     const int lane = (int)(j & 3), pair = lane >> 1;
-    const float u1 = (float)((w[2 * pair] >> 8) + 1u) * 5.9604644775390625e-08f;      // (0, 1], exact in fp32
-    const float u2 = (float)(w[2 * pair + 1] >> 8) * 5.9604644775390625e-08f;         // [0, 1)
-    const float radius = sqrtf(-2.0f * logf(u1));
-    const float theta = 6.283185307179586f * u2;
-    return radius * ((lane & 1) ? sinf(theta) : cosf(theta));
+    return gaphilox::box_muller(w[2 * pair], w[2 * pair + 1], lane & 1);
 }
 
 __global__ __launch_bounds__(256) void step_kernel(GaSdeStep s, int phase)

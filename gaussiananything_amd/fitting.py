@@ -1,10 +1,14 @@
-"""Fitting 2D surfels to posed views on the device -- the host side of include/ga_fit.h (HIP kernels, csrc/surfel_fit.hip).
+"""Fitting 2D surfels to posed views on the device -- the host side of include/ga_fit.h and include/ga_densify.h (HIP kernels,
+csrc/surfel_fit.hip and csrc/surfel_densify.hip).
 
     to_raw           the inverse of the activation: a Gaussian tensor [N,13] -> the raw parameters the optimiser moves
     step_table       the per-step Adam step sizes and bias corrections, computed in double, stored fp32
     SurfelFitter     one iteration = ga_fit_activate -> ga_surfel_forward -> post-processing -> the two loss forwards -> the two loss
                      backwards -> ga_fit_pack_grads -> ga_surfel_backward -> ga_fit_adam -> ga_fit_advance: one chain on one stream,
-                     captured once and replayed as one HIP graph per iteration
+                     captured once and replayed as one HIP graph per iteration; with ``densify=`` the number of surfels changes
+                     between stretches of iterations (clone / split / prune rounds and opacity resets)
+    densify_and_prune  one clone / split / prune round on raw, m, v and the three densification statistics
+    reset_opacity      the opacity reset: raw opacity capped at logit(cap), its Adam moments zeroed
 
 Nothing in an iteration reads the device: the Adam step index is a device word (``ga_fit_advance`` moves it), the loss weights are device
 tensors the loss backwards read as ``grad_out``, the loss terms go to a device history that ``loss_history()`` reads back in one copy, and
@@ -14,12 +18,13 @@ an exponential, rotation a normalised quaternion.  There is no CPU fallback: wit
 
 Two fits of the same input are NOT bit-identical: ``ga_surfel_backward`` sums with floating-point atomics.
 
-Not built: densification, pruning, opacity reset, LPIPS, view mini-batching on the device (``set_views`` between ``step`` calls is the
+Not built: LPIPS, view mini-batching on the device (``set_views`` between ``step`` calls is the
 way).  ``GaussianRenderer2DGS.render`` and the autograd path are untouched.
 """
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
 
 import numpy as np
@@ -92,6 +97,168 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+# ---- adaptive density control (include/ga_densify.h) ---------------------------------------------------------------------------------
+def _is_int(x):
+    return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+
+def _is_num(x):
+    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+
+def _check_densify_scalars(grad_threshold, min_opacity, percent_dense, extent, max_screen_size, seed, max_points):
+    if not _is_num(grad_threshold) or math.isnan(grad_threshold) or grad_threshold < 0:
+        raise ValueError("grad_threshold must be a non-negative number (inf: nothing is cloned or split)")
+    if not _is_num(min_opacity) or not 0.0 <= min_opacity <= 1.0:
+        raise ValueError("min_opacity must lie in [0, 1]")
+    if not _is_num(percent_dense) or not (0.0 <= percent_dense < math.inf):
+        raise ValueError("percent_dense must be a non-negative finite number")
+    if not _is_num(extent) or not (0.0 < extent < math.inf):
+        raise ValueError("extent (the scene radius) must be a positive finite number")
+    if not _is_num(max_screen_size) or not (0.0 <= max_screen_size < math.inf):
+        raise ValueError("max_screen_size must be a non-negative finite number (0: no pruning by size)")
+    if not _is_int(seed) or not 0 <= seed < 1 << 64:
+        raise ValueError("seed must be an integer in [0, 2^64)")
+    if max_points is not None and (not _is_int(max_points) or max_points < 1):
+        raise ValueError("max_points must be None or a positive integer")
+
+
+@dataclasses.dataclass(frozen=True)
+class DensifyConfig:
+    """When and how ``SurfelFitter`` changes the number of surfels; the defaults are 2DGS's published settings.  ``t`` is the number
+    of iterations taken.  A clone / split / prune round runs after iteration t when ``start <= t <= stop`` and ``t % every == 0``; its
+    pruning by size (``max_screen_size``, in pixels of radius, and 0.1 * extent in world units) applies when ``t > screen_size_from``;
+    the opacities are reset after iteration t when ``t <= stop`` and ``t % opacity_reset_every == 0`` (0: never), after the round of
+    the same iteration.  ``extent`` is the scene radius.  A round that would leave more than ``max_points`` surfels only prunes."""
+    extent: float
+    start: int = 500
+    stop: int = 15000
+    every: int = 100
+    grad_threshold: float = 2e-4
+    min_opacity: float = 0.05
+    percent_dense: float = 0.01
+    max_screen_size: float = 20
+    screen_size_from: int = 3000
+    opacity_reset_every: int = 3000
+    max_points: int | None = None
+    seed: int = 0
+
+    def __post_init__(self):
+        _check_densify_scalars(self.grad_threshold, self.min_opacity, self.percent_dense, self.extent, self.max_screen_size, self.seed,
+                               self.max_points)
+        for name in ("start", "stop", "every", "screen_size_from", "opacity_reset_every"):
+            if not _is_int(getattr(self, name)) or getattr(self, name) < 0:
+                raise ValueError(f"{name} must be a non-negative integer")
+        if self.every < 1:
+            raise ValueError("every must be at least 1")
+        if self.stop < self.start:
+            raise ValueError("stop must not be smaller than start")
+
+
+def _as_config(densify):
+    if densify is None or isinstance(densify, DensifyConfig):
+        return densify
+    if isinstance(densify, dict):
+        known = {f.name for f in dataclasses.fields(DensifyConfig)}
+        if set(densify) - known:
+            raise ValueError(f"densify: unknown fields {sorted(set(densify) - known)}")
+        if "extent" not in densify:
+            raise ValueError("densify: extent (the scene radius) is required")
+        return DensifyConfig(**densify)
+    raise TypeError("densify must be None, a DensifyConfig or a dict of its fields")
+
+
+def _check_points(raw, m, v):
+    for name, t in (("raw", raw), ("m", m), ("v", v)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 torch.Tensor")
+    for name, t in (("raw", raw), ("m", m), ("v", v)):
+        if t.device.type != "cuda":
+            raise ValueError(f"{name} is on {t.device}: density control only runs on an MI355X (HIP) device; there is no CPU path")
+        if t.device != raw.device or t.dim() != 2 or t.shape[1] != 13 or t.shape[0] < 1 or t.shape != raw.shape:
+            raise ValueError(f"{name} must be [N,13] on {raw.device}, not {list(t.shape)} on {t.device}")
+    if raw.shape[0] > 1 << 30:
+        raise ValueError("more than 2^30 surfels")
+    return int(raw.shape[0])
+
+
+def _activated(L, raw, stream):
+    """ga_fit_activate into buffers of its own -> (opacities, scales, rotations)"""
+    N, dev = raw.shape[0], raw.device
+    means, opac, colors = (torch.empty(shape, dtype=torch.float32, device=dev) for shape in ((N, 3), (N,), (N, 3)))
+    scales, rots, inv_norm = (torch.empty(shape, dtype=torch.float32, device=dev) for shape in ((N, 2), (N, 4), (N,)))
+    args = _lib.GaFitActivateArgs(N, 0, raw.data_ptr(), means.data_ptr(), opac.data_ptr(), colors.data_ptr(), scales.data_ptr(),
+                                  rots.data_ptr(), inv_norm.data_ptr())
+    _lib.check(L.ga_fit_activate(ctypes.byref(args), stream), "ga_fit_activate")
+    return opac, scales, rots
+
+
+def densify_and_prune(raw, m, v, grad_accum, denom, max_radius, *, grad_threshold, min_opacity, percent_dense, extent,
+                      max_screen_size=0, seed=0, round=0, max_points=None, return_noise=False):
+    """One clone / split / prune round (include/ga_densify.h: ga_densify) on the raw parameters [N,13], their Adam moments and the
+    three statistics ``ga_fit_accumulate`` keeps (float32 [N], int32 [N], int32 [N]) -> ``raw, m, v, parent, counts``: views of the
+    first N' rows of buffers of 2 N rows, ``parent`` [N'] int32 the source row of every output row, ``counts`` a dict of ``N_before``,
+    ``N_after``, ``kept``, ``cloned``, ``split``, ``pruned``, ``prune_only`` (and ``noise`` [N,4] with ``return_noise``).  A round that
+    would leave more than ``max_points`` rows is run again as a prune-only round.  One synchronisation: the read of the counts.  N' may
+    be 0: the tensors are then empty.  The inputs are left as they are."""
+    _check_densify_scalars(grad_threshold, min_opacity, percent_dense, extent, max_screen_size, seed, max_points)
+    if not _is_int(round) or not 0 <= round < 1 << 32:
+        raise ValueError("round must be an integer in [0, 2^32)")
+    N = _check_points(raw, m, v)
+    for name, t, dtype in (("grad_accum", grad_accum, torch.float32), ("denom", denom, torch.int32), ("max_radius", max_radius, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+            raise TypeError(f"{name} must be a torch.Tensor of {dtype}")
+        if t.device != raw.device or tuple(t.shape) != (N,):
+            raise ValueError(f"{name} must be [{N}] on {raw.device}, not {list(t.shape)} on {t.device}")
+    L, dev = _lib.lib(), raw.device
+    raw, m, v, grad_accum, denom, max_radius = (t.detach().contiguous() for t in (raw, m, v, grad_accum, denom, max_radius))
+    with torch.cuda.device(dev):
+        s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        opac, scales, rots = _activated(L, raw, s)
+        out_raw, out_m, out_v = (torch.empty(2 * N, 13, dtype=torch.float32, device=dev) for _ in range(3))
+        parent = torch.empty(2 * N, dtype=torch.int32, device=dev)
+        noise = torch.empty(N, 4, dtype=torch.float32, device=dev) if return_noise else None
+        out_counts = torch.zeros(_lib.GA_DENSIFY_COUNTS, dtype=torch.int64, device=dev)
+        ws = torch.empty(int(L.ga_densify_workspace_bytes(N)), dtype=torch.uint8, device=dev)
+        a = _lib.GaDensifyArgs()
+        a.num_points, a.flags, a.round, a.seed = N, 0, int(round), int(seed)
+        a.grad_threshold, a.min_opacity, a.percent_dense = float(grad_threshold), float(min_opacity), float(percent_dense)
+        a.extent, a.max_screen_size = float(extent), float(max_screen_size)
+        a.raw, a.m, a.v = raw.data_ptr(), m.data_ptr(), v.data_ptr()
+        a.opacities, a.scales, a.rotations = opac.data_ptr(), scales.data_ptr(), rots.data_ptr()
+        a.grad_accum, a.denom, a.max_radius = grad_accum.data_ptr(), denom.data_ptr(), max_radius.data_ptr()
+        a.out_raw, a.out_m, a.out_v, a.parent = out_raw.data_ptr(), out_m.data_ptr(), out_v.data_ptr(), parent.data_ptr()
+        a.noise_out, a.out_counts = _ptr(noise), out_counts.data_ptr()
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        _lib.check(L.ga_densify(ctypes.byref(a), s), "ga_densify")
+        c = out_counts.cpu().tolist()
+        if max_points is not None and c[0] > max_points:
+            a.flags = _lib.GA_DENSIFY_PRUNE_ONLY
+            _lib.check(L.ga_densify(ctypes.byref(a), s), "ga_densify")
+            c = out_counts.cpu().tolist()
+    n = int(c[0])
+    counts = {"N_before": N, "N_after": n, "kept": int(c[1]), "cloned": int(c[2]), "split": int(c[3]), "pruned": int(c[4]),
+              "prune_only": bool(a.flags & _lib.GA_DENSIFY_PRUNE_ONLY)}
+    if return_noise:
+        counts["noise"] = noise
+    return out_raw[:n], out_m[:n], out_v[:n], parent[:n], counts
+
+
+def reset_opacity(raw, m, v, cap=0.01):
+    """The opacity reset, in place (include/ga_densify.h: ga_fit_reset_opacity): the raw opacity of every surfel is capped at
+    logit(cap), computed in double and rounded once, and the opacity column of the Adam moments is zeroed -> raw"""
+    if not _is_num(cap) or not 0.0 < cap < 1.0:
+        raise ValueError("cap must lie in (0, 1)")
+    N = _check_points(raw, m, v)
+    if not (raw.is_contiguous() and m.is_contiguous() and v.is_contiguous()):
+        raise ValueError("raw, m and v are changed in place: they must be contiguous")
+    with torch.cuda.device(raw.device):
+        a = _lib.GaFitResetOpacityArgs(N, math.log(cap / (1.0 - cap)), raw.data_ptr(), m.data_ptr(), v.data_ptr())
+        s = ctypes.c_void_p(torch.cuda.current_stream(raw.device).cuda_stream)
+        _lib.check(_lib.lib().ga_fit_reset_opacity(ctypes.byref(a), s), "ga_fit_reset_opacity")
+    return raw
+
+
 class SurfelFitter:
     """Adam on the raw parameters of N surfels against V posed target views; see the module docstring.
 
@@ -101,13 +268,20 @@ class SurfelFitter:
 
     The loss is ``l2 * MSE + l1 * L1 + ssim * (1 - SSIM) + lambda_normal * normal + lambda_dist * dist + lambda_alpha * |alpha - mask|``
     as ``losses.photometric_loss`` and ``losses.geometric_loss`` define the terms (``normal`` / ``mask`` as in ``geometric_loss``).
+
+    ``densify`` (a ``DensifyConfig`` or a dict of its fields; None: the number of surfels never changes and nothing below exists):
+    ``ga_fit_accumulate`` joins the captured chain, ``step`` ends a stretch of iterations wherever a clone / split / prune round or
+    an opacity reset is due, runs it, and captures the iteration again for the new number of surfels.  ``densify_now()`` runs a round
+    at once, ``num_points`` is the present N, ``densify_log`` lists ``(step, N_before, N_after, cloned, split, pruned)`` per round.
     """
 
     def __init__(self, gaussians, cam_view, cam_view_proj, tanfov, targets, *, mask=None, normal=None, bg=None,
                  l2=0.0, l1=0.8, ssim=0.2, lambda_normal=0.05, lambda_dist=0.0, lambda_alpha=0.0, lr=None,
-                 betas=(0.9, 0.999), eps=1e-15, max_steps=DEFAULT_MAX_STEPS, visible_only=False, check_every=50, capacity=None):
+                 betas=(0.9, 0.999), eps=1e-15, max_steps=DEFAULT_MAX_STEPS, visible_only=False, check_every=50, capacity=None,
+                 densify=None):
         # ---- everything the host can see is checked before anything is enqueued --------------------------------------------------
         lr = _check_lr(dict(DEFAULT_LR) if lr is None else lr)
+        self._densify = _as_config(densify)
         tensors = [("gaussians", gaussians), ("cam_view", cam_view), ("cam_view_proj", cam_view_proj), ("targets", targets)]
         tensors += [(k, t) for k, t in (("mask", mask), ("normal", normal), ("bg", bg)) if t is not None]
         for name, t in tensors:
@@ -144,20 +318,17 @@ class SurfelFitter:
         self.betas, self.eps, self.visible_only = (float(betas[0]), float(betas[1])), float(eps), bool(visible_only)
         self.weights = dict(l2=float(l2), l1=float(l1), ssim=float(ssim), lambda_normal=float(lambda_normal),
                             lambda_dist=float(lambda_dist), lambda_alpha=float(lambda_alpha))
-        self.plan = _lib.GaFitPlan()
-        _lib.check(self._L.ga_fit_plan(N, V, H, W, ctypes.byref(self.plan)), "ga_fit_plan")
+        self._round, self.densify_log = 0, []
 
         def f32(*shape):
             return torch.zeros(shape, dtype=torch.float32, device=dev)
 
         with torch.cuda.device(dev):
-            # state
-            self._raw, self._m, self._v, self._raw_grad = raw, f32(N, 13), f32(N, 13), f32(N, 13)
+            # state that does not depend on N
             self._counter = torch.zeros(1, dtype=torch.int32, device=dev)
             self._seen = torch.zeros(4, dtype=torch.int64, device=dev)
             self._history = f32(max_steps, _lib.GA_FIT_HISTORY_COLS)
             self._table = step_table(lr, self.betas, max_steps).to(dev)
-            self._snap = [torch.empty_like(self._raw), torch.empty_like(self._m), torch.empty_like(self._v), torch.empty_like(self._counter)]
             # static inputs
             self._view, self._proj = f32(V, 16), f32(V, 16)
             self._targets = f32(V, 3, H, W)
@@ -165,27 +336,13 @@ class SurfelFitter:
             self._normal = f32(V, 3, H, W) if normal is not None else None
             self._bg = torch.ones(3, dtype=torch.float32, device=dev) if bg is None else bg.detach().float().reshape(3).clone()
             self._copy_views(cam_view, cam_view_proj, targets, mask, normal)
-            # the activated arrays, one buffer laid out by the plan
-            pl = self.plan
-            self._act_buffer = torch.zeros(pl.workspace_bytes + 256, dtype=torch.uint8, device=dev)
-            base = (-self._act_buffer.data_ptr()) % 256
-
-            def section(off, *shape):
-                n = int(np.prod(shape)) * 4
-                return self._act_buffer[base + off:base + off + n].view(torch.float32).view(*shape)
-
-            self._means, self._opac, self._colors = section(pl.means, N, 3), section(pl.opacities, N), section(pl.colors, N, 3)
-            self._scales, self._rots, self._inv_norm = section(pl.scales, N, 2), section(pl.rotations, N, 4), section(pl.inv_norm, N)
             # rasterizer outputs, the maps of render's differentiable branch and their gradients
             self._color, self._allmap = f32(V, 3, H, W), f32(V, 7, H, W)
-            self._radii = torch.zeros(V, N, dtype=torch.int32, device=dev)
             self._image, self._rend_normal, self._depth = f32(V, 3, H, W), f32(V, 3, H, W), f32(V, 1, H, W)
             self._alpha, self._dist = f32(V, 1, H, W), f32(V, 1, H, W)
             self._g_image, self._g_rend_normal = f32(V, 3, H, W), f32(V, 3, H, W)
             self._g_depth, self._g_dist, self._g_alpha = f32(V, 1, H, W), f32(V, 1, H, W), f32(V, 1, H, W)
             self._g_color, self._g_allmap = f32(V, 3, H, W), f32(V, 7, H, W)
-            self._g_means, self._g_opac, self._g_colors = f32(N, 3), f32(N), f32(N, 3)
-            self._g_scales, self._g_rots = f32(N, 2), f32(N, 4)
             # loss means and their weights: divided by V (the mean over the views), SSIM with a minus sign (the term is 1 - SSIM)
             w = self.weights
             self._photo_out, self._geo_out = f32(V, 3), f32(V, 3)
@@ -198,15 +355,55 @@ class SurfelFitter:
                 raise ValueError(f"views of {H} x {W} are out of the loss kernels' range")
             self._photo_ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
             self._geo_ws = torch.zeros(gbytes, dtype=torch.uint8, device=dev)
-            ws = SurfelWorkspace(dev, N, V, H, W, int(capacity) if capacity is not None else default_capacity(N, V))
-            self._fwd = SurfelForwardPlan._bound((self._means, self._opac, self._colors, self._scales, self._rots, self._view, self._proj,
-                                                  self._bg), H, W, 1.0, ws, for_backward=True,
-                                                 outputs=(self._color, self._allmap, self._radii))
             self._steps = self._snap_steps = 0
             self._graph = None
             self._side = torch.cuda.Stream(dev)
+            self._allocate_points(raw, None, None, int(capacity) if capacity is not None else default_capacity(N, V))
             self._bind()
             self._warm_up_and_capture()
+
+    def _allocate_points(self, raw, m, v, capacity, seg_capacity=0):
+        """everything whose size depends on the number of surfels: the state and its snapshot, the activated arrays, the radii, the
+        per-surfel gradients, the densification statistics, the launch plan, the rasterizer workspace and the bound forward"""
+        dev, V, H, W = self.device, self.V, self.H, self.W
+        N = self.N = int(raw.shape[0])
+
+        def f32(*shape):
+            return torch.zeros(shape, dtype=torch.float32, device=dev)
+
+        self.plan = _lib.GaFitPlan()
+        _lib.check(self._L.ga_fit_plan(N, V, H, W, ctypes.byref(self.plan)), "ga_fit_plan")
+        with torch.cuda.device(dev):
+            self._raw, self._raw_grad = raw.contiguous(), f32(N, 13)
+            self._m = f32(N, 13) if m is None else m.contiguous()
+            self._v = f32(N, 13) if v is None else v.contiguous()
+            if self._densify is not None:
+                self._grad_accum = f32(N)
+                self._denom, self._max_radius = (torch.zeros(N, dtype=torch.int32, device=dev) for _ in range(2))
+            self._snap = [torch.empty_like(t) for t in self._state()]
+            # the activated arrays, one buffer laid out by the plan
+            pl = self.plan
+            self._act_buffer = torch.zeros(pl.workspace_bytes + 256, dtype=torch.uint8, device=dev)
+            base = (-self._act_buffer.data_ptr()) % 256
+
+            def section(off, *shape):
+                n = int(np.prod(shape)) * 4
+                return self._act_buffer[base + off:base + off + n].view(torch.float32).view(*shape)
+
+            self._means, self._opac, self._colors = section(pl.means, N, 3), section(pl.opacities, N), section(pl.colors, N, 3)
+            self._scales, self._rots, self._inv_norm = section(pl.scales, N, 2), section(pl.rotations, N, 4), section(pl.inv_norm, N)
+            self._radii = torch.zeros(V, N, dtype=torch.int32, device=dev)
+            self._g_means, self._g_opac, self._g_colors = f32(N, 3), f32(N), f32(N, 3)
+            self._g_scales, self._g_rots = f32(N, 2), f32(N, 4)
+            ws = SurfelWorkspace(dev, N, V, H, W, capacity, seg_capacity)
+            self._fwd = SurfelForwardPlan._bound((self._means, self._opac, self._colors, self._scales, self._rots, self._view, self._proj,
+                                                  self._bg), H, W, 1.0, ws, for_backward=True,
+                                                 outputs=(self._color, self._allmap, self._radii))
+
+    def _state(self):
+        """what a snapshot holds: raw, m, v and the step counter; with density control also its three statistics"""
+        state = (self._raw, self._m, self._v, self._counter)
+        return state if self._densify is None else state + (self._grad_accum, self._denom, self._max_radius)
 
     # ---- validation and static inputs ------------------------------------------------------------------------------------------
     def _check_views(self, cam_view, cam_view_proj, targets, mask, normal):
@@ -277,6 +474,10 @@ class SurfelFitter:
         self._a_bwd = _lib.GaSurfelBackwardArgs(fwd, self._g_color.data_ptr(), self._g_allmap.data_ptr(), self._scratch.data_ptr(),
                                                 self._scratch.numel(), self._g_means.data_ptr(), self._g_opac.data_ptr(),
                                                 self._g_colors.data_ptr(), self._g_scales.data_ptr(), self._g_rots.data_ptr())
+        if self._densify is not None:
+            self._a_acc = _lib.GaFitAccumulateArgs(N, V, self.tanfov, 0, self._g_means.data_ptr(), self._means.data_ptr(),
+                                                   self._radii.data_ptr(), self._view.data_ptr(), self._grad_accum.data_ptr(),
+                                                   self._denom.data_ptr(), self._max_radius.data_ptr())
         b1, b2 = self.betas
         self._a_adam = _lib.GaFitAdamArgs(
             N, V, _lib.GA_FIT_VISIBLE_ONLY if self.visible_only else 0, self.max_steps, self._g_means.data_ptr(),
@@ -304,16 +505,18 @@ class SurfelFitter:
         _lib.check(L.ga_geo_loss_backward(ref(self._a_geo), s), "ga_geo_loss_backward")
         _lib.check(L.ga_fit_pack_grads(ref(self._a_pack), s), "ga_fit_pack_grads")
         _lib.check(L.ga_surfel_backward(ref(self._a_bwd), s), "ga_surfel_backward")
+        if self._densify is not None:
+            _lib.check(L.ga_fit_accumulate(ref(self._a_acc), s), "ga_fit_accumulate")
         _lib.check(L.ga_fit_adam(ref(self._a_adam), s), "ga_fit_adam")
         _lib.check(L.ga_fit_advance(ref(self._a_adv), s), "ga_fit_advance")
 
     def _save(self):
-        for dst, src in zip(self._snap, (self._raw, self._m, self._v, self._counter)):
+        for dst, src in zip(self._snap, self._state()):
             dst.copy_(src)
         self._snap_steps = self._steps
 
     def _restore(self):
-        for src, dst in zip(self._snap, (self._raw, self._m, self._v, self._counter)):
+        for src, dst in zip(self._snap, self._state()):
             dst.copy_(src)
         self._seen.zero_()
         self._steps = self._snap_steps
@@ -327,7 +530,8 @@ class SurfelFitter:
             self._side.wait_stream(main)
             with torch.cuda.stream(self._side):
                 self._save()
-                row = self._history[self._steps].clone()
+                at = min(self._steps, self.max_steps - 1)      # (the row the device counter, which stops at the last one, selects)
+                row = self._history[at].clone()
                 while True:
                     self._enqueue()
                     seen = self._seen.cpu()
@@ -335,7 +539,7 @@ class SurfelFitter:
                     if int(seen[0]) == 0:
                         break
                     self._grow(seen)
-                self._history[self._steps].copy_(row)
+                self._history[at].copy_(row)
                 self._side.synchronize()
                 self._graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(self._graph, stream=self._side):
@@ -352,7 +556,9 @@ class SurfelFitter:
         """Run n iterations: n replays of the captured graph.  Every ``check_every`` iterations and at the end the overflow words are
         read (the one synchronisation) and a device snapshot of raw, m, v and the step counter is taken; if a forward in between did
         not fit its workspace, the snapshot is restored, the workspace grown, the iteration captured again and the iterations since
-        the snapshot are run again."""
+        the snapshot are run again.  With density control a stretch also ends at every iteration after which a round or an opacity
+        reset is due: the overflow words are read first (an overflowed stretch is run again before anything else), then the round
+        runs on the statistics of the iterations since the last one."""
         n = int(n)
         if n < 0:
             raise ValueError("n must not be negative")
@@ -361,18 +567,96 @@ class SurfelFitter:
         target = self._steps + n
         with torch.cuda.device(self.device):
             while self._steps < target:
-                k = min(self.check_every - (self._steps - self._snap_steps), target - self._steps)
+                due = self._next_event(self._steps) if self._densify is not None else None
+                stop = target if due is None else min(target, due)
+                k = min(self.check_every - (self._steps - self._snap_steps), stop - self._steps)
                 for _ in range(k):
                     self._graph.replay()
                 self._steps += k
                 seen = self._seen.cpu()
-                if int(seen[0]) == 0:
-                    self._save()
-                else:
+                if int(seen[0]) != 0:
                     self._restore()
                     self._grow(seen)
                     self._warm_up_and_capture()
+                elif self._steps == due:
+                    self._run_event()
+                else:
+                    self._save()
         return self
+
+    # ---- density control -------------------------------------------------------------------------------------------------------
+    def _round_due(self, t):
+        c = self._densify
+        return c.start <= t <= c.stop and t % c.every == 0
+
+    def _reset_due(self, t):
+        c = self._densify
+        return c.opacity_reset_every > 0 and 0 < t <= c.stop and t % c.opacity_reset_every == 0
+
+    def _next_event(self, t):
+        """the first iteration count above t after which a round or a reset is due, or None"""
+        c = self._densify
+        first = -(-max(c.start, t + 1) // c.every) * c.every
+        due = [first] if first <= c.stop else []
+        if c.opacity_reset_every > 0 and (t // c.opacity_reset_every + 1) * c.opacity_reset_every <= c.stop:
+            due.append((t // c.opacity_reset_every + 1) * c.opacity_reset_every)
+        return min(due) if due else None
+
+    def _run_event(self, force_round=False):
+        """what is due after iteration ``self._steps``: the round, then the reset; then a snapshot -- after a round the new capture
+        takes it"""
+        t = self._steps
+        entry = self._densify_round() if force_round or self._round_due(t) else None
+        if self._reset_due(t) and not force_round:
+            reset_opacity(self._raw, self._m, self._v)
+        if self._graph is None:
+            self._warm_up_and_capture()
+        else:
+            self._save()
+        return entry
+
+    def _densify_round(self):
+        c, before = self._densify, self.N
+        size = c.max_screen_size if self._steps > c.screen_size_from else 0
+        raw, m, v, _, n = densify_and_prune(self._raw, self._m, self._v, self._grad_accum, self._denom, self._max_radius,
+                                            grad_threshold=c.grad_threshold, min_opacity=c.min_opacity, percent_dense=c.percent_dense,
+                                            extent=c.extent, max_screen_size=size, seed=c.seed, round=self._round,
+                                            max_points=c.max_points)
+        if n["N_after"] == 0:
+            raise RuntimeError(f"the densify round after iteration {self._steps} pruned every one of the {before} surfels")
+        self._round += 1
+        entry = (self._steps, before, n["N_after"], n["cloned"], n["split"], n["pruned"])
+        self.densify_log.append(entry)
+        self._resize(raw.clone(), m.clone(), v.clone())
+        return entry
+
+    def _resize(self, raw, m, v):
+        """another number of surfels: everything sized by N anew (the statistics zeroed), the workspace scaled with N, every argument
+        block rebuilt; the captured graph is dropped -- ``_warm_up_and_capture`` is the caller's next call"""
+        ws, before = self._fwd.ws, self.N
+        self._graph = None
+        capacity = max(ws.capacity, -(-ws.capacity * int(raw.shape[0]) // before))
+        self._allocate_points(raw, m, v, capacity, ws.seg_capacity)
+        self._bind()
+
+    def densify_now(self):
+        """Run one clone / split / prune round at once, on the statistics gathered since the last one -> its ``densify_log`` entry
+        ``(step, N_before, N_after, cloned, split, pruned)``"""
+        if self._densify is None:
+            raise RuntimeError("this fitter was constructed without densify=")
+        with torch.cuda.device(self.device):
+            return self._run_event(force_round=True)
+
+    def densify_stats(self) -> dict:
+        """copies of the three statistics the next round decides on: ``grad_accum`` [N] float32, ``denom`` and ``max_radius`` [N] int32"""
+        if self._densify is None:
+            raise RuntimeError("this fitter was constructed without densify=")
+        return {"grad_accum": self._grad_accum.clone(), "denom": self._denom.clone(), "max_radius": self._max_radius.clone()}
+
+    @property
+    def num_points(self) -> int:
+        """the present number of surfels"""
+        return self.N
 
     @property
     def steps(self) -> int:
@@ -398,27 +682,52 @@ class SurfelFitter:
         return int(self._fwd.ws.status()[_lib.GA_STATUS_NUM_RENDERED].cpu())
 
     def state_dict(self) -> dict:
-        """copies of raw, m, v and the loss history, and the number of steps taken: what ``load_state_dict`` of a fitter of the same N
-        and ``max_steps`` continues from (views, weights and learning rates are the constructor's)"""
-        return {"raw": self._raw.clone(), "m": self._m.clone(), "v": self._v.clone(), "steps": self._steps,
-                "history": self._history[:self._steps].clone()}
+        """copies of raw, m, v and the loss history, the number of steps taken, N and, with density control, its three statistics and
+        the number of rounds run: what ``load_state_dict`` of a fitter of the same ``max_steps`` continues from (views, weights,
+        learning rates and the densify settings are the constructor's)"""
+        state = {"raw": self._raw.clone(), "m": self._m.clone(), "v": self._v.clone(), "steps": self._steps,
+                 "history": self._history[:self._steps].clone(), "N": self.N, "round": self._round}
+        if self._densify is not None:
+            state.update(self.densify_stats())
+        return state
 
     def load_state_dict(self, state: dict):
         steps = int(state["steps"])
         if not 0 <= steps <= self.max_steps:
             raise ValueError(f"the state has taken {steps} steps, this fitter's table has {self.max_steps} rows")
+        n = int(state["raw"].shape[0]) if state["raw"].dim() == 2 else 0
         for k in ("raw", "m", "v"):
-            if tuple(state[k].shape) != (self.N, 13):
-                raise ValueError(f"state[{k!r}] must be [{self.N}, 13], not {list(state[k].shape)}")
+            if n < 1 or tuple(state[k].shape) != (n, 13):
+                raise ValueError(f"state[{k!r}] must be [N, 13], not {list(state[k].shape)}")
+        if int(state.get("N", n)) != n:
+            raise ValueError(f"state['N'] is {state['N']}, state['raw'] holds {n} rows")
         if tuple(state["history"].shape) != (steps, _lib.GA_FIT_HISTORY_COLS):
             raise ValueError("state['history'] must hold one row per step taken")
+        stats = ("grad_accum", "denom", "max_radius") if self._densify is not None and "grad_accum" in state else ()
+        for k in stats:
+            if tuple(state[k].shape) != (n,):
+                raise ValueError(f"state[{k!r}] must be [{n}], not {list(state[k].shape)}")
         with torch.cuda.device(self.device):
-            for dst, k in ((self._raw, "raw"), (self._m, "m"), (self._v, "v")):
+            dev = self.device
+            if n != self.N:       # a state of another N: everything sized by N anew, a new capture below
+                self._resize(*(state[k].detach().to(dev, torch.float32).clone() for k in ("raw", "m", "v")))
+            else:
+                for dst, k in ((self._raw, "raw"), (self._m, "m"), (self._v, "v")):
+                    dst.copy_(state[k])
+                if self._densify is not None:
+                    for t in (self._grad_accum, self._denom, self._max_radius):
+                        t.zero_()
+            for dst, k in zip((getattr(self, "_grad_accum", None), getattr(self, "_denom", None), getattr(self, "_max_radius", None)),
+                              stats):
                 dst.copy_(state[k])
+            self._round = int(state.get("round", 0))
             self._history[:steps].copy_(state["history"])
             self._counter.fill_(min(steps, self.max_steps - 1))
             self._steps = steps
-            self._save()
+            if self._graph is None:
+                self._warm_up_and_capture()
+            else:
+                self._save()
         return self
 
     def gaussians(self) -> torch.Tensor:
