@@ -307,6 +307,19 @@ __device__ __forceinline__ bool seg_context(const uint32_t *__restrict__ tile_st
     return true;
 }
 
+// The depth distortion is a variance: sum_{j<i} w_i w_j (m_i - m_j)^2, and every expression the backward forms from the moments
+// W, M1, M2 -- m^2 W - 2 m M1 + M2, m W - M1, W M2 - M1^2 and the cross-segment prefix -- is unchanged when one constant is taken off
+// every m.  With the raw m (0.88 +- 0.005 for a scene of 0.2 across seen from 1.7) those expressions cancel to 1e-4 of their terms and
+// fp32 leaves two digits: the distortion gradient alone was 2.4e-2 off the float64 oracle (tests/test_surfel_backward_gpu.py, one
+// output-channel group at a time; a plain fp32 evaluation of the raw moments does no better).  So the moments are taken about the m of
+// the tile's front-most list entry, m - m0 = kM near (1 / depth0 - 1 / depth): the same constant in the sums and the gradient kernels.
+__device__ __forceinline__ float tile_rd0(const uint32_t *__restrict__ tile_start, const uint32_t *__restrict__ point_list,
+                                          const float *__restrict__ brec, const SegCtx &c)
+{
+    const uint32_t id0 = point_list[tile_start[c.vt]];   // (the segment exists, so the list has a first entry)
+    return __builtin_amdgcn_rcpf(brec[(c.vbase + id0) * kBRec + 8]);   // Tw[2]: the depth of its centre, beyond the near plane
+}
+
 // stage the segment: records to the field planes (kFields of them), survivor masks of my pixel
 // (xbits / ybits, threads 0..127 only: the tile columns / rows inside the cull box of entry threadIdx.x -- an interval each)
 template <int kFields>
@@ -467,6 +480,7 @@ __global__ __launch_bounds__(256) void surfel_bwd_sums_kernel(const uint32_t *__
     SegCtx c;
     if (!seg_context(tile_start, pl, dm, c, blockIdx.x)) return;
     const float kM = kFar / (kFar - kNear);
+    const float rd0 = tile_rd0(tile_start, point_list, brec, c);
     float T = pl.Tseg[(size_t)blockIdx.x * 256 + threadIdx.x];   // (T_start since the prefix launch)
     bool done = !c.inside || T < 0.0001f;
     float W = 0.f, M1 = 0.f, M2 = 0.f, A = 0.f;
@@ -501,7 +515,7 @@ __global__ __launch_bounds__(256) void surfel_bwd_sums_kernel(const uint32_t *__
                 if (!f.ok) continue;
                 const float test_T = T * (1.0f - f.alpha);
                 if (test_T < 0.0001f) { done = true; break; }
-                const float w = f.alpha * T, mz = kM * (1.0f - kNear * __builtin_amdgcn_rcpf(f.depth));
+                const float w = f.alpha * T, mz = kM * kNear * (rd0 - __builtin_amdgcn_rcpf(f.depth));   // m - m0 (tile_rd0)
                 W += w; M1 += mz * w; M2 += mz * mz * w;
                 A += w * ((pg.gC[0] * GA_BF(15) + pg.gC[1] * GA_BF(16) + pg.gC[2] * GA_BF(17)) +
                           (pg.gN[0] * GA_BF(12) + pg.gN[1] * GA_BF(13) + pg.gN[2] * GA_BF(14)) + pg.gD * f.depth);
@@ -550,7 +564,7 @@ struct PairShared {
     uint32_t tail_id[4][kTailBatch];
 };
 
-struct PixC { float gC[3], gN[3], gD, gDist, W, M1, M2, Vtot, Tfb, gMed, Tfin; };
+struct PixC { float gC[3], gN[3], gD, gDist, W, M1, M2, Vtot, Tfb, gMed, Tfin, rd0; };   // (W, M1, M2 about m0; rd0: tile_rd0)
 struct PairV { float w, mz, rd, vi; };
 
 __device__ __forceinline__ PairV pair_value(const float *__restrict__ b, const PairFwd &f, float T, const PixC &pc)
@@ -559,7 +573,7 @@ __device__ __forceinline__ PairV pair_value(const float *__restrict__ b, const P
     PairV o;
     o.rd = __builtin_amdgcn_rcpf(f.depth);
     o.w = f.alpha * T;
-    o.mz = kM * (1.0f - kNear * o.rd);
+    o.mz = kM * kNear * (pc.rd0 - o.rd);   // m - m0
     const float Dq = o.mz * o.mz * pc.W - 2.0f * o.mz * pc.M1 + pc.M2;
     o.vi = (pc.gC[0] * GA_BF(15) + pc.gC[1] * GA_BF(16) + pc.gC[2] * GA_BF(17)) +
            (pc.gN[0] * GA_BF(12) + pc.gN[1] * GA_BF(13) + pc.gN[2] * GA_BF(14)) + pc.gD * f.depth + pc.gDist * Dq;
@@ -676,6 +690,7 @@ __global__ __launch_bounds__(256) void surfel_bwd_grad_kernel(const uint32_t *__
         pc.Vtot = tot.w + 2.0f * pg.gDist * (tot.x * tot.z - tot.y * tot.y);
         pc.Tfb = T_final * ((pg.gC[0] * bg[0] + pg.gC[1] * bg[1] + pg.gC[2] * bg[2]) - pg.gA);
         pc.gMed = pg.gMed; pc.Tfin = T_final;
+        pc.rd0 = tile_rd0(tile_start, point_list, brec, c);
     }
     float P = pre.w + pc.gDist * (pc.W * pre.z - 2.0f * pc.M1 * pre.y + pc.M2 * pre.x);
     unsigned long long m[2];
@@ -761,6 +776,7 @@ __global__ __launch_bounds__(256) void surfel_bwd_grad_kernel(const uint32_t *__
                 q.gD = pr.pix[6][pix]; q.gDist = pr.pix[7][pix]; q.W = pr.pix[8][pix]; q.M1 = pr.pix[9][pix];
                 q.M2 = pr.pix[10][pix]; q.Vtot = pr.pix[11][pix]; q.Tfb = pr.pix[12][pix];
                 q.gMed = pr.pix[13][pix]; q.Tfin = pr.pix[14][pix];
+                q.rd0 = pc.rd0;      // (one per tile)
                 const float qx = tx0 + (float)lx, qy = ty0 + (float)ly;
                 const float *b = &sh.rec[0][e];
                 PairFwd f;
@@ -834,6 +850,7 @@ __global__ __launch_bounds__(256) void surfel_bwd_grad_big_kernel(const uint32_t
         pc.Vtot = tot.w + 2.0f * pg.gDist * (tot.x * tot.z - tot.y * tot.y);
         pc.Tfb = T_final * ((pg.gC[0] * bg[0] + pg.gC[1] * bg[1] + pg.gC[2] * bg[2]) - pg.gA);
         pc.gMed = pg.gMed; pc.Tfin = T_final;
+        pc.rd0 = tile_rd0(tile_start, point_list, brec, c);
     }
     float P = pre.w + pc.gDist * (pc.W * pre.z - 2.0f * pc.M1 * pre.y + pc.M2 * pre.x);
     for (uint32_t w = threadIdx.x; w < kBwdChunk * (kGRec + 1); w += 256) (&sgrad[0][0])[w] = 0.0f;

@@ -32,10 +32,12 @@ def quat_to_rot(q):
                         2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1).reshape(q.shape[:-1] + (3, 3))
 
 
-def render(means3D, opacities, colors, scales, rotations, cam_view, cam_view_proj, bg, H, W, scale_modifier=1.0):
-    """All tensors float64; matrices in the reference's row-vector convention.  Returns (color [3,H,W], allmap [7,H,W]) =
-    (expected depth, alpha, normal xyz, median depth, distortion), differentiable w.r.t. the five Gaussian tensors."""
-    dt = torch.float64
+def render(means3D, opacities, colors, scales, rotations, cam_view, cam_view_proj, bg, H, W, scale_modifier=1.0, dtype=torch.float64):
+    """All tensors of ``dtype`` (float64: the oracle; float32: the same statements in the kernels' number format, which pins how far a
+    plain fp32 evaluation lies from it -- tests/test_surfel_backward_cpu.py); matrices in the reference's row-vector convention.
+    Returns (color [3,H,W], allmap [7,H,W]) = (expected depth, alpha, normal xyz, median depth, distortion), differentiable w.r.t.
+    the five Gaussian tensors."""
+    dt = dtype
     V, VP = cam_view.to(dt), cam_view_proj.to(dt)
     py, px = torch.meshgrid(torch.arange(H, dtype=dt), torch.arange(W, dtype=dt), indexing="ij")
     ndcx, ndcy = (2 * px + 1) / W - 1, (2 * py + 1) / H - 1            # pixel = ((ndc + 1) * size - 1) / 2
@@ -48,6 +50,7 @@ def render(means3D, opacities, colors, scales, rotations, cam_view, cam_view_pro
     C = torch.zeros(3, H, W, dtype=dt)
     Dp = torch.zeros(H, W, dtype=dt); Nrm = torch.zeros(3, H, W, dtype=dt); dist = torch.zeros(H, W, dtype=dt)
     M1 = torch.zeros(H, W, dtype=dt); M2 = torch.zeros(H, W, dtype=dt); median = torch.zeros(H, W, dtype=dt)
+    alive = torch.ones(H, W, dtype=torch.bool)                              # pixels whose walk has not ended
     for i in order.tolist():
         tu, tv, n = R[i, :, 0] * scales[i, 0] * scale_modifier, R[i, :, 1] * scales[i, 1] * scale_modifier, R[i, :, 2]
         p0 = means3D[i]
@@ -89,7 +92,13 @@ def render(means3D, opacities, colors, scales, rotations, cam_view, cam_view_pro
         alpha = torch.where(raw.detach() > 0.99, torch.full_like(raw, 0.99), raw)              # clamp: no gradient above it
         nv = n @ V[:3, :3]
         nv = nv * torch.sign(-torch.dot((torch.cat([p0, z0 + 1]) @ V)[:3], nv)).detach()        # facing the camera
-        ok = ((alpha >= 1.0 / 255.0) & (depth >= NEAR) & (T * (1 - alpha) >= 1e-4)).detach() & in_rect
+        # The walk of a pixel ENDS at the first pair that would take T below 1e-4 (oracle/surfel_raster.c: done = true): that pair
+        # and every later one take no part, also a later one with a smaller alpha that would pass the test on its own.  (Until the
+        # opaque scenes of tests/test_surfel_backward_gpu.py this file only skipped the failing pair and went on: alpha off by up to
+        # 3e-3 against the C oracle there, gradients of occluded surfels by several per cent.)
+        cand = ((alpha >= 1.0 / 255.0) & (depth >= NEAR)).detach() & in_rect & alive
+        ok = cand & (T * (1 - alpha) >= 1e-4).detach()
+        alive = alive & ~(cand & ~ok)
         wgt = torch.where(ok, alpha * T, torch.zeros_like(T))
         m = FAR / (FAR - NEAR) * (1 - NEAR / depth)
         dist = dist + torch.where(ok, (m * m * (1 - T) + M2 - 2 * m * M1) * wgt, torch.zeros_like(T))

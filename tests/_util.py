@@ -40,4 +40,5 @@ def ws_artifacts(ws, N, V, H, W):
     with np.errstate(invalid="ignore"):
         bbox = np.stack([rec[..., 8] - rx, rec[..., 9] - ry, rec[..., 8] + rx, rec[..., 9] + ry], -1)
     return dict(D=D, overflow=int(st[1]), max_tile=int(st[2]), tile_start=tile_start, rect=rect,
-                point_list=point_list, bbox=bbox, tiles=tiles)
+                point_list=point_list, bbox=bbox, tiles=tiles,
+                cull_centre=np.stack([rec[..., 8], rec[..., 9]], -1), cull_half=np.stack([rx, ry], -1))
