@@ -1,4 +1,4 @@
-"""Element-wise error bounds of the bf16-MFMA kernels against a float64 reference computed from the exact bf16 / fp32 values the
+"""Element-wise error bounds of the bf16-MFMA kernels (and, at the end, of the row kernels around them) against a float64 reference computed from the exact bf16 / fp32 values the
 kernel reads.  Every function takes and returns float64 torch tensors (any device).
 
 Model.  u = 2^-24 is the unit roundoff of fp32 round-to-nearest, ub = 2^-8 that of bf16; gamma(n) = n u / (1 - n u) bounds the
@@ -255,3 +255,185 @@ def attention(qh, dq, kh, dk, v, c=1.0, n_acc=64, rel_c=0.0, lazy=8.0, tiles=Non
             Pe = Pe + gamma(4) * (o.abs() + Pe)
             out[ps, qs], bound[ps, qs], dom[ps, qs] = o, bf16_store(o, Pe), S.argmax(-1)
     return out, bound, dom
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Row kernels (dit_ops.hip: rmsnorm_modulate, small_linear, shift_bias; decode_ops.hip: tiny_mlp_silu, layernorm_modulate,
+# tiny_attention, surfel_head).  A value is a pair (ref, P): the float64 reference and a bound on |fp32 value - ref|.  fl_add / fl_mul
+# propagate such pairs through one fp32 operation (one rounding each; a contracted multiply-add rounds once and is counted as two);
+# a division costs DIV_REL.  The references use the fp32 values of the kernels' literals (F32 below).
+#
+# Math library.  The relative errors of the OCML functions these kernels call are MEASURED, each function alone on a dense grid over
+# the argument range of the cases (tools/row_math_probe.hip, output in profiles/row_math_error.txt); the constant is twice the worst
+# relative error observed, because a grid can miss the worst argument.  Nothing else here is measured.
+TANHF_REL = 2 * 1.6974e-07          # tanhf on [-32, 32]: 2.848 u   (profiles/row_math_error.txt, lines "tanhf")
+SINF_REL = 2 * 1.2237e-07           # sinf on [0, 1024]: 2.053 u    (lines "sinf")
+COSF_REL = 2 * 1.2371e-07           # cosf on [0, 1024]: 2.076 u    (lines "cosf")
+EXPF_REL = 2 * 1.3989e-06           # expf on [-40, 40]: 23.47 u, growing with |x|   (lines "expf", the first two)
+EXPF_FREQ_REL = 2 * 4.1033e-07      # expf on [-9.25, 0], the timestep frequencies: 6.884 u   (line "expf", the third)
+LOG1PF_REL = 2 * 1.1831e-07         # log1pf on [1e-18, 1e18]: 1.985 u   (lines "log1pf")
+SQRTF_REL = 2 * 5.9605e-08          # sqrtf on [1e-30, 1e10]: 1.000 u (correctly rounded)   (lines "sqrtf")
+MATH_ARG_MAX = 40.0                 # |argument| of tanhf / expf the grids cover (sinf / cosf: 1024)
+# a / b: correctly rounded under hipcc's default; counted as a 1-ulp v_rcp_f32 and a product so that it also holds for a reciprocal
+DIV_REL = 2 * U + U
+LOG2E_REL = abs(LOG2E_F32 - 1 / math.log(2.0)) * math.log(2.0)     # the fp32 literal 0x1.715476p+0 of __expf against log2 e
+SILU_DMAX = 1.0999                  # max |silu'(x)| (at x ~ 2.4)
+GELU_TANH_DMAX = 1.13               # max |gelu_tanh'(x)| (at x ~ 2.4; 1.1290)
+XSECH2_MAX = 0.4478                 # max |x| sech^2(x) (at x ~ 0.7717): what a relative error of tanh's argument becomes
+FLUSH_ABS = 2.0 ** -120             # v_exp_f32 returns 0 below 2^-126 and overflows above 2^128: |v| e^-|v| there is below this
+
+
+def F32(x):
+    """the fp32 value of a literal, as float64"""
+    return float(torch.tensor(x, dtype=torch.float32))
+
+
+def fl_add(a, Pa, b, Pb=0.0):
+    """v = fl(a_hat + b_hat): (a + b, Pa + Pb + u (|a + b| + Pa + Pb))"""
+    v = a + b
+    P = Pa + Pb
+    return v, P + U * (v.abs() + P)
+
+
+def fl_mul(a, Pa, b, Pb=0.0):
+    """v = fl(a_hat b_hat): (a b, |a| Pb + |b| Pa + Pa Pb, then one rounding)"""
+    v = a * b
+    aa = a.abs() if torch.is_tensor(a) else abs(a)
+    ab = b.abs() if torch.is_tensor(b) else abs(b)
+    P = aa * Pb + ab * Pa + Pa * Pb
+    return v, P + U * (v.abs() + P)
+
+
+def wave_sum(abs_sum, n):
+    """|fp32 sum - exact sum| of n fp32 terms with absolute sum abs_sum, in whatever order and grouping (per-lane partial sums, the
+    xor butterfly): a tree of n - 1 additions, gamma(n) abs_sum"""
+    return gamma(n) * abs_sum
+
+
+def rms_rows(x, eps):
+    """rs = rsqrtf(fl(fl(sum of D fp32 squares) / D) + eps) of rows x [..., D] (exact fp32 values): (r_ref, rho), |rs - r| <= rho r.
+    row_scale with D + 1 partials: the squares are rounded too."""
+    D = x.shape[-1]
+    return row_scale(x.pow(2).sum(-1, keepdim=True), D + 1, D, eps)
+
+
+def layernorm_stats(x, eps):
+    """Two-pass LayerNorm statistics of rows x [..., D] (exact fp32 values), as layernorm_modulate_kernel / surfel_head_kernel (mode 1)
+    form them: mean = fl(wave sum / D), centred values e = fl(x - mean), rs = rsqrtf(fl(fl(sum e^2) / D) + eps).
+      mean:  |dm| <= Dm = (1 + u) gamma(D) sum|x| / D + u |mean|
+      e:     |e_hat - e| <= De = Dm + u (|e| + Dm)
+      q = sum e_hat^2:  |q_hat - q| <= sum (2 |e| De + De^2) + gamma(D + 1) sum (|e| + De)^2   (squares rounded, D - 1 additions)
+      A = q / D + eps:  |A_hat - A| <= dq / D + gamma(2) (A + dq / D);  rsqrt halves the relative error x of A, then RSQRT_REL
+    Returns (e, De, r, rho): y = e r is evaluated by the caller with |rs - r| <= rho r."""
+    D = x.shape[-1]
+    mean = x.mean(-1, keepdim=True)
+    Dm = (1 + U) * wave_sum(x.abs().sum(-1, keepdim=True), D) / D + U * mean.abs()
+    e = x - mean
+    De = Dm + U * (e.abs() + Dm)
+    q = e.pow(2).sum(-1, keepdim=True)
+    dq = (2 * e.abs() * De + De * De).sum(-1, keepdim=True) + gamma(D + 1) * (e.abs() + De).pow(2).sum(-1, keepdim=True)
+    A = q / D + eps
+    xa = (dq / D + gamma(2) * (A + dq / D)) / A
+    r = torch.rsqrt(A)
+    rho = (1 + xa / (2 * (1 - xa))) * (1 + RSQRT_REL) - 1
+    return e, De, r, rho
+
+
+def fast_exp_rel(x):
+    """relative error of __expf(x) = v_exp_f32(fl(log2e_f32 x)): the product's rounding and the literal's error move the exponent by
+    |x| log2 e (u + LOG2E_REL), a factor exp(|x| (u + LOG2E_REL)); then the 1-ulp exp2"""
+    return torch.exp(x.abs() * (U + LOG2E_REL)) * (1 + EXP2_REL) - 1
+
+
+def _one_plus_exp_rel(v, P, e_rel):
+    """relative error of fl(1 + e_hat), e = exp(-v_hat), e_hat = e (1 + e_rel): e_rel e / (1 + e) + u, with e / (1 + e) at its largest
+    over |v_hat - v| <= P (it falls as v grows); shared by silu and sigmoid"""
+    e = torch.exp(-(v - P))
+    return e_rel * e / (1 + e) + U * (1 + e_rel)
+
+
+def silu(v, P):
+    """silu_f(v_hat) = fl(v_hat / fl(1 + __expf(-v_hat))), |v_hat - v| <= P: (silu(v), bound).  Input error: SILU_DMAX P.  Evaluation at
+    v_hat: e_hat = e (1 + fast_exp_rel), d = 1 + e has relative error e_rel e / (1 + e) + u, then the division."""
+    ref = v * torch.sigmoid(v)
+    prop = SILU_DMAX * P
+    ed = _one_plus_exp_rel(v, P, fast_exp_rel(v.abs() + P))
+    rel = (1 + ed / (1 - ed)) * (1 + DIV_REL) - 1
+    return ref, prop + rel * (ref.abs() + prop) + FLUSH_ABS
+
+
+def sigmoid(v, P):
+    """fl(1 / fl(1 + expf(-v_hat))) with OCML's expf (|v| + P <= MATH_ARG_MAX): (sigmoid(v), bound); |sigmoid'| <= 1 / 4"""
+    ref = torch.sigmoid(v)
+    prop = 0.25 * P
+    ed = _one_plus_exp_rel(v, P, EXPF_REL)
+    rel = (1 + ed / (1 - ed)) * (1 + DIV_REL) - 1
+    return ref, prop + rel * (ref + prop)
+
+
+SOFTPLUS_THRESHOLD = 20.0
+
+
+def softplus(v, P):
+    """v_hat > 20 ? v_hat : log1pf(expf(v_hat)) (F.softplus, threshold 20): (ref, bound) with the threshold in the reference.
+    |softplus'| <= 1: P.  e_hat = e (1 + EXPF_REL) moves log1p by at most e EXPF_REL / (1 + e) <= EXPF_REL min(e, 1); log1pf its own
+    relative error.  Where |v - 20| <= P the two sides may take different branches: they differ by log1p(e^-20) < 2.1e-9 there."""
+    e = torch.exp(v.clamp(max=SOFTPLUS_THRESHOLD + 1.0))
+    lp = torch.log1p(e)
+    ref = torch.where(v > SOFTPLUS_THRESHOLD, v, lp)
+    b = P + EXPF_REL * e / (1 + e) + LOG1PF_REL * (lp + P)
+    return ref, b + torch.where((v - SOFTPLUS_THRESHOLD).abs() <= P, 2.1e-9, 0.0)
+
+
+def tanh(v, P):
+    """tanhf(v_hat), |v| + P <= MATH_ARG_MAX: (tanh(v), bound); |tanh'| <= 1"""
+    ref = torch.tanh(v)
+    return ref, P + TANHF_REL * (ref.abs() + P)
+
+
+def gelu_tanh(v, P):
+    """gelu_tanh_f(v_hat) = 0.5f v (1 + tanhf(c0 (v + c1 v v v))) with the fp32 literals c0, c1: (ref, bound).  The argument of tanh:
+    three products, a sum of two terms of equal sign and a product -- gamma(5) relative, at most XSECH2_MAX gamma(5) on tanh; tanhf its
+    own error; 1 + t one rounding; 0.5f v is exact, the last product one rounding.  Input error: GELU_TANH_DMAX P."""
+    c0, c1 = F32(0.7978845608028654), F32(0.044715)
+    t = torch.tanh(c0 * (v + c1 * v * v * v))
+    ref = 0.5 * v * (1 + t)
+    dt = XSECH2_MAX * gamma(5) + TANHF_REL * (t.abs() + XSECH2_MAX * gamma(5))
+    prop = GELU_TANH_DMAX * P
+    ev = 0.5 * (v.abs() + P) * (dt + U * (1 + t + dt + P))          # evaluated at v_hat: |v_hat| <= |v| + P, t_hat <= t + P
+    return ref, prop + ev + U * (ref.abs() + prop + ev)
+
+
+def normalize4(v, P):
+    """F.normalize of rows v [..., 4] carrying errors P: g = fl(v_hat fl(1 / max(sqrtf(n2), 1e-12f))), n2 the fp32 sum of four squares.
+    The norm n is 1-Lipschitz in v, so the input errors move it by at most |P|_2; n2 (four squares, three additions) carries a
+    relative error x = gamma(5), which the square root halves (x / (2 (1 - x))), then SQRTF_REL: dn in all.  max(., 1e-12f) does not
+    increase it; the reciprocal DIV_REL, the product one rounding.  A row of exact zeros (P = 0) gives 0 / 1e-12 = 0 with bound 0."""
+    n = v.pow(2).sum(-1, keepdim=True).sqrt()
+    pn = P.pow(2).sum(-1, keepdim=True).sqrt() if torch.is_tensor(P) else torch.zeros_like(n)
+    x = gamma(5)
+    dn = pn + (n + pn) * ((1 + x / (2 * (1 - x))) * (1 + SQRTF_REL) - 1)
+    m = n.clamp_min(F32(1e-12))
+    rho_m = dn / (m - dn).clamp_min(1e-300)
+    rho = (1 + rho_m) * (1 + DIV_REL) - 1
+    ref = v / m
+    b = (P * (1 + rho) + v.abs() * rho) / m
+    return ref, b + U * (ref.abs() + b)
+
+
+def sincos_arg(t, j):
+    """arg = fl(t fr_j), fr_j = expf(fl(fl(-c32 j) / 128)) against t exp(-ln(10000) j / 128): (ref, P).  The exponent a = ln(10000) j / 128
+    <= 9.21 carries the literal's relative error and one rounding (/ 128 is exact); expf then EXPF_FREQ_REL; the product one rounding.
+    t [B, 1], j [128] float64."""
+    c = math.log(10000.0)
+    dc = abs(F32(9.210340371976184) - c) / c
+    a = c * j / 128.0
+    f_rel = torch.exp(a * (dc + U)) * (1 + EXPF_FREQ_REL) - 1
+    ref = t * torch.exp(-a)
+    return ref, ref.abs() * ((1 + f_rel) * (1 + U) - 1)
+
+
+def sin_cos(arg, P):
+    """(cos ref, cos bound, sin ref, sin bound) of cosf / sinf(arg_hat), |arg_hat - arg| <= P, |arg| <= 1024: both 1-Lipschitz"""
+    c, s = torch.cos(arg), torch.sin(arg)
+    return c, P + COSF_REL * (c.abs() + P), s, P + SINF_REL * (s.abs() + P)
