@@ -129,7 +129,8 @@ __global__ __launch_bounds__(64) void control_kernel(int64_t n, int nparts, doub
     if (j1 >= ngrid) ctl[GA_ODE_DONE] = 1.0;
 }
 
-__global__ __launch_bounds__(256) void accept_kernel(int64_t n, float *__restrict__ y, const float *__restrict__ y1, float *__restrict__ k0,
+// (k0 is the caller's k[0], the buffer kp.k[0] reads in the same loop: no __restrict__ on it)
+__global__ __launch_bounds__(256) void accept_kernel(int64_t n, float *__restrict__ y, const float *__restrict__ y1, float *k0,
                                                      KPtrs kp, const double *__restrict__ ctl, const double *__restrict__ t_grid,
                                                      float *__restrict__ out)
 {
