@@ -191,6 +191,13 @@ class GaFitAdvanceArgs(ctypes.Structure):
                [("ssim_bias", ctypes.c_float), ("reserved", ctypes.c_int32), ("status", ctypes.c_void_p), ("seen", ctypes.c_void_p)]
 
 
+class GaFitSelectArgs(ctypes.Structure):
+    """include/ga_fit.h: GaFitSelectArgs"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("pool_views", "batch_views", "height", "width", "max_steps", "flags")] + \
+               [(n, ctypes.c_void_p) for n in ("schedule", "counter", "pool_view", "pool_proj", "pool_targets", "pool_mask", "pool_normal",
+                                               "view", "proj", "targets", "mask", "normal", "selected")]
+
+
 class GaFitAccumulateArgs(ctypes.Structure):
     """include/ga_densify.h: GaFitAccumulateArgs"""
     _fields_ = [("num_points", ctypes.c_int32), ("num_views", ctypes.c_int32), ("tanfov", ctypes.c_float), ("reserved", ctypes.c_int32)] + \
@@ -215,6 +222,7 @@ class GaFitResetOpacityArgs(ctypes.Structure):
 
 GA_DENSIFY_PRUNE_ONLY, GA_DENSIFY_COUNTS = 1, 8
 GA_FIT_PARAMS, GA_FIT_GROUPS, GA_FIT_TABLE_COLS, GA_FIT_HISTORY_COLS, GA_FIT_VISIBLE_ONLY = 13, 5, 8, 8, 1
+GA_FIT_SELECT_U8_TARGETS = 1
 GA_FPS_VARIANT_REGISTER, GA_FPS_VARIANT_STREAMING = 0, 1
 GA_PHOTO_LOSS_SAVE = 1
 GA_GEO_LOSS_TARGET, GA_GEO_LOSS_NORMALS = 1, 2
@@ -227,7 +235,7 @@ EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspa
            "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward",
            "ga_photo_loss_plan", "ga_photo_loss_workspace_bytes", "ga_photo_loss_forward", "ga_photo_loss_backward",
            "ga_geo_loss_plan", "ga_geo_loss_workspace_bytes", "ga_geo_loss_forward", "ga_geo_loss_backward",
-           "ga_fit_plan", "ga_fit_activate", "ga_fit_pack_grads", "ga_fit_adam", "ga_fit_advance",
+           "ga_fit_plan", "ga_fit_activate", "ga_fit_pack_grads", "ga_fit_adam", "ga_fit_advance", "ga_fit_select_views",
            "ga_fit_accumulate", "ga_densify_workspace_bytes", "ga_densify", "ga_fit_reset_opacity")
 
 _lib = None
@@ -319,7 +327,8 @@ def lib():
         L.ga_fit_plan.restype = ctypes.c_int
         L.ga_fit_plan.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(GaFitPlan)]
         for name, struct in (("ga_fit_activate", GaFitActivateArgs), ("ga_fit_pack_grads", GaFitPackArgs), ("ga_fit_adam", GaFitAdamArgs),
-                             ("ga_fit_advance", GaFitAdvanceArgs), ("ga_fit_accumulate", GaFitAccumulateArgs),
+                             ("ga_fit_advance", GaFitAdvanceArgs), ("ga_fit_select_views", GaFitSelectArgs),
+                             ("ga_fit_accumulate", GaFitAccumulateArgs),
                              ("ga_densify", GaDensifyArgs), ("ga_fit_reset_opacity", GaFitResetOpacityArgs)):
             getattr(L, name).restype = ctypes.c_int
             getattr(L, name).argtypes = [ctypes.POINTER(struct), ctypes.c_void_p]

@@ -1,8 +1,9 @@
 // surfel_fit.hip -- the glue of one surfel-fitting iteration (include/ga_fit.h): activation of the raw parameters into the five arrays
 // ga_surfel_forward reads, the adjoint of the renderer's post-processing (the gradients of the two loss backwards packed into the
-// grad_color / grad_others ga_surfel_backward reads), the chain rule to raw space fused with the Adam step, and the advance of the
-// device-side step counter.  Four streaming kernels; with the existing forward, loss and backward launches they form one chain on one
-// stream that a HIP graph replays once per iteration: nothing here takes a host value that changes between iterations.
+// grad_color / grad_others ga_surfel_backward reads), the chain rule to raw space fused with the Adam step, the advance of the
+// device-side step counter, and the selection of the iteration's views from a pool on the device.  Five streaming kernels; with the
+// existing forward, loss and backward launches they form one chain on one stream that a HIP graph replays once per iteration: nothing
+// here takes a host value that changes between iterations.
 //
 // Built with -ffp-contract=off: the Adam step and the chain rule are bit-identical to the operation-by-operation restatement the tests
 // hold them to (tests/_fit_ref.py); division and square root are hipcc's correctly rounded defaults.
@@ -10,6 +11,7 @@
 //   pack      one lane per 4 consecutive pixels of a view (1 when H*W % 4 != 0), as surfel_post.hip: up to 19 planes read, 10 written
 //   adam      one lane per surfel: the row of the step table is table[*counter], read from the device
 //   advance   one thread, a launch of its own behind adam: the history row, then ++*counter (clamped)
+//   select    mini-batches only, the first launch: row *counter of the view schedule names the pool views copied into the batch buffers
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -202,6 +204,68 @@ __global__ __launch_bounds__(64) void fit_advance_kernel(GaFitAdvanceArgs a)
     }
 }
 
+constexpr int kSelectMaxBlocks = 2048;   // a streaming copy: enough workgroups to fill the device, the rest of the work grid-strided
+
+template <int VEC> struct SelectUnit { typedef uint32_t type; };
+template <> struct SelectUnit<4> { typedef uint4 type; };
+
+// The views of iteration *counter, from the pool into the buffers the rest of the chain reads.  blockIdx.y strides over the slots of the
+// batch, blockIdx.x over the units (VEC elements) of a slot: its three target planes, then its mask, then its three normal planes.  The
+// first workgroup of a slot also moves the two camera matrices and the index.  Integer moves: no float operation touches an fp32 value.
+template <int VEC, bool U8>
+__global__ __launch_bounds__(kFitThreads) void fit_select_kernel(GaFitSelectArgs a, int64_t hw)
+{
+    typedef typename SelectUnit<VEC>::type unit_t;
+    int t = *a.counter;                         // the device-side step: the same word for every lane of the launch
+    t = t < 0 ? 0 : (t >= a.max_steps ? a.max_steps - 1 : t);
+    const int32_t *row = a.schedule + (int64_t)t * a.batch_views;
+    const int64_t q = hw / VEC;                 // units per plane
+    const int64_t n_targets = 3 * q, n_mask = a.pool_mask ? q : 0, n_normal = a.pool_normal ? 3 * q : 0;
+    const int64_t units = n_targets + n_mask + n_normal;
+    const int64_t stride = (int64_t)gridDim.x * kFitThreads;
+    for (int b = blockIdx.y; b < a.batch_views; b += gridDim.y) {
+        int p = row[b];
+        p = p < 0 ? 0 : (p >= a.pool_views ? a.pool_views - 1 : p);   // the host validates the table; this only keeps the reads inside the pool
+        if (blockIdx.x == 0) {
+            const int k = threadIdx.x & 15;
+            if (threadIdx.x < 16)
+                reinterpret_cast<uint32_t *>(a.view)[(int64_t)b * 16 + k] = reinterpret_cast<const uint32_t *>(a.pool_view)[(int64_t)p * 16 + k];
+            else if (threadIdx.x < 32)
+                reinterpret_cast<uint32_t *>(a.proj)[(int64_t)b * 16 + k] = reinterpret_cast<const uint32_t *>(a.pool_proj)[(int64_t)p * 16 + k];
+            else if (threadIdx.x == 32 && a.selected)
+                a.selected[b] = p;
+        }
+        for (int64_t u = (int64_t)blockIdx.x * kFitThreads + threadIdx.x; u < units; u += stride) {
+            if (u < n_targets) {
+                unit_t *dst = reinterpret_cast<unit_t *>(a.targets) + (int64_t)b * n_targets + u;
+                if (U8) {
+                    const uint8_t *src = static_cast<const uint8_t *>(a.pool_targets) + ((int64_t)p * n_targets + u) * VEC;
+                    float f[VEC];
+                    if (VEC == 4) {
+                        const uint32_t w = *reinterpret_cast<const uint32_t *>(src);
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) f[e] = (float)((w >> (8 * e)) & 255u) / 255.0f;
+                    } else {
+                        f[0] = (float)src[0] / 255.0f;
+                    }
+                    float *d = reinterpret_cast<float *>(dst);
+                    if (VEC == 4) *reinterpret_cast<float4 *>(d) = make_float4(f[0], f[1], f[2], f[VEC - 1]);
+                    else d[0] = f[0];
+                } else {
+                    *dst = (static_cast<const unit_t *>(a.pool_targets) + (int64_t)p * n_targets)[u];
+                }
+            } else if (u < n_targets + n_mask) {
+                const int64_t r = u - n_targets;
+                (reinterpret_cast<unit_t *>(a.mask) + (int64_t)b * n_mask)[r] = (reinterpret_cast<const unit_t *>(a.pool_mask) + (int64_t)p * n_mask)[r];
+            } else {
+                const int64_t r = u - n_targets - n_mask;
+                (reinterpret_cast<unit_t *>(a.normal) + (int64_t)b * n_normal)[r] =
+                    (reinterpret_cast<const unit_t *>(a.pool_normal) + (int64_t)p * n_normal)[r];
+            }
+        }
+    }
+}
+
 static bool fit_shape_ok(int32_t n, int32_t v, int32_t h, int32_t w)
 {
     return n >= 1 && v >= 1 && v <= 65535 && h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31) &&
@@ -281,6 +345,38 @@ extern "C" int ga_fit_adam(const GaFitAdamArgs *a, void *stream)
     (void)hipGetLastError();
     hipLaunchKernelGGL(ga::fit_adam_kernel, dim3((unsigned)pl.grid_adam), dim3((unsigned)pl.threads), 0,
                        reinterpret_cast<hipStream_t>(stream), *a);
+    return hipGetLastError() == hipSuccess ? GA_OK : GA_ERR_LAUNCH;
+}
+
+extern "C" int ga_fit_select_views(const GaFitSelectArgs *a, void *stream)
+{
+    if (!a || !a->schedule || !a->counter || !a->pool_view || !a->pool_proj || !a->pool_targets || !a->view || !a->proj || !a->targets)
+        return GA_ERR_NULL_ARG;
+    if ((a->pool_mask == nullptr) != (a->mask == nullptr) || (a->pool_normal == nullptr) != (a->normal == nullptr)) return GA_ERR_NULL_ARG;
+    if (a->flags & ~GA_FIT_SELECT_U8_TARGETS) return GA_ERR_BAD_FLAGS;
+    if (a->pool_views < 1 || a->batch_views < 1 || a->batch_views > a->pool_views || a->height < 1 || a->width < 1 || a->max_steps < 1 ||
+        (int64_t)a->height * a->width >= ((int64_t)1 << 31))
+        return GA_ERR_BAD_SHAPE;
+    const int64_t hw = (int64_t)a->height * a->width;
+    // as ga_fit_pack_grads: 16 bytes per lane need whole planes of 4 elements and 16-byte aligned buffers (a view into a larger tensor
+    // may not be); otherwise one element per lane
+    uintptr_t bits = 0;
+    for (const void *p : {(const void *)a->pool_view, (const void *)a->pool_proj, a->pool_targets, (const void *)a->pool_mask,
+                          (const void *)a->pool_normal, (const void *)a->view, (const void *)a->proj, (const void *)a->targets,
+                          (const void *)a->mask, (const void *)a->normal})
+        bits |= reinterpret_cast<uintptr_t>(p);
+    const bool vec4 = hw % 4 == 0 && (bits & 15) == 0;
+    const bool u8 = (a->flags & GA_FIT_SELECT_U8_TARGETS) != 0;
+    const int64_t units = (hw / (vec4 ? 4 : 1)) * (3 + (a->pool_mask ? 1 : 0) + (a->pool_normal ? 3 : 0));
+    const int64_t gy = a->batch_views < ga::kSelectMaxBlocks ? a->batch_views : ga::kSelectMaxBlocks;
+    const int64_t want = (units + ga::kFitThreads - 1) / ga::kFitThreads, cap = ga::kSelectMaxBlocks / gy;
+    const dim3 grid((unsigned)(want < cap ? want : cap), (unsigned)gy), block((unsigned)ga::kFitThreads);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    (void)hipGetLastError();
+    if (vec4 && u8) hipLaunchKernelGGL((ga::fit_select_kernel<4, true>), grid, block, 0, s, *a, hw);
+    else if (vec4) hipLaunchKernelGGL((ga::fit_select_kernel<4, false>), grid, block, 0, s, *a, hw);
+    else if (u8) hipLaunchKernelGGL((ga::fit_select_kernel<1, true>), grid, block, 0, s, *a, hw);
+    else hipLaunchKernelGGL((ga::fit_select_kernel<1, false>), grid, block, 0, s, *a, hw);
     return hipGetLastError() == hipSuccess ? GA_OK : GA_ERR_LAUNCH;
 }
 

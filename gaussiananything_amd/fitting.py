@@ -3,10 +3,14 @@ csrc/surfel_fit.hip and csrc/surfel_densify.hip).
 
     to_raw           the inverse of the activation: a Gaussian tensor [N,13] -> the raw parameters the optimiser moves
     step_table       the per-step Adam step sizes and bias corrections, computed in double, stored fp32
+    view_schedule    the table of view mini-batches: which views of a pool every iteration renders (epochs of random permutations)
     SurfelFitter     one iteration = ga_fit_activate -> ga_surfel_forward -> post-processing -> the two loss forwards -> the two loss
                      backwards -> ga_fit_pack_grads -> ga_surfel_backward -> ga_fit_adam -> ga_fit_advance: one chain on one stream,
                      captured once and replayed as one HIP graph per iteration; with ``densify=`` the number of surfels changes
-                     between stretches of iterations (clone / split / prune rounds and opacity resets)
+                     between stretches of iterations (clone / split / prune rounds and opacity resets); with
+                     ``batch_views=B`` the views given are a pool of P kept on the device and ``ga_fit_select_views`` heads the
+                     chain: it copies the B views row ``*counter`` of the schedule names into the buffers the chain reads
+                     
     densify_and_prune  one clone / split / prune round on raw, m, v and the three densification statistics
     reset_opacity      the opacity reset: raw opacity capped at logit(cap), its Adam moments zeroed
 
@@ -18,8 +22,8 @@ an exponential, rotation a normalised quaternion.  There is no CPU fallback: wit
 
 Two fits of the same input are NOT bit-identical: ``ga_surfel_backward`` sums with floating-point atomics.
 
-Not built: LPIPS, view mini-batching on the device (``set_views`` between ``step`` calls is the
-way).  ``GaussianRenderer2DGS.render`` and the autograd path are untouched.
+Not built: LPIPS, a view pool in host memory, per-view image sizes.  ``GaussianRenderer2DGS.render`` and the autograd path are
+untouched.  The view schedule, like the parametrisation, is the project's own definition: no reference trainer runs here to pin it.
 """
 from __future__ import annotations
 
@@ -79,6 +83,49 @@ def step_table(lr: dict, betas=(0.9, 0.999), max_steps: int = DEFAULT_MAX_STEPS)
         out[:, k] = np.array([_lr_at(lr[name], int(s), max_steps) for s in range(max_steps)], np.float64) / bc1
     out[:, len(GROUPS)] = np.sqrt(1.0 - np.power(b2, t + 1.0))
     return torch.from_numpy(out.astype(np.float32))
+
+
+def view_schedule(max_steps: int, pool_views: int, batch_views: int, seed: int = 0) -> torch.Tensor:
+    """-> int32 [max_steps, B] (host): row t names the B views of a pool of P that iteration t renders.  The definition, in numpy::
+
+        rng = np.random.default_rng(seed)
+        n = -(-P // B)                                     # rows per epoch: ceil(P / B)
+        rows = []
+        while len(rows) < max_steps:
+            perm = rng.permutation(P)                      # one epoch
+            rows.extend(np.concatenate([perm, perm[:n * B - P]]).reshape(n, B))
+        table = np.stack(rows[:max_steps]).astype(np.int32)
+
+    An epoch is one permutation of the pool cut into consecutive rows; a short last row is completed from the start of the same
+    permutation, so no row holds a view twice and every epoch covers every view.  ``B > P`` is refused."""
+    for name, x in (("max_steps", max_steps), ("pool_views", pool_views), ("batch_views", batch_views)):
+        if not _is_int(x) or x < 1:
+            raise ValueError(f"{name} must be a positive integer")
+    if batch_views > pool_views:
+        raise ValueError(f"batch_views = {batch_views} exceeds the pool of {pool_views} views")
+    if not _is_int(seed) or seed < 0:
+        raise ValueError("seed must be a non-negative integer")
+    P, B = int(pool_views), int(batch_views)
+    rng = np.random.default_rng(int(seed))
+    n = -(-P // B)
+    rows = []
+    while len(rows) < max_steps:
+        perm = rng.permutation(P)
+        rows.extend(np.concatenate([perm, perm[:n * B - P]]).reshape(n, B))
+    return torch.from_numpy(np.stack(rows[:max_steps]).astype(np.int32))
+
+
+def _check_schedule(schedule, max_steps, pool_views, batch_views):
+    """a schedule of the caller's -> a contiguous int32 host tensor [max_steps, B] with every value in [0, P): the kernel clamps what
+    it reads, which keeps it inside the pool but would hide a wrong table"""
+    if not isinstance(schedule, torch.Tensor) or schedule.is_floating_point() or schedule.is_complex() or schedule.dtype == torch.bool:
+        raise TypeError("view_schedule must be an integer torch.Tensor")
+    if tuple(schedule.shape) != (max_steps, batch_views):
+        raise ValueError(f"view_schedule must be [max_steps, batch_views] = [{max_steps}, {batch_views}], not {list(schedule.shape)}")
+    host = schedule.detach().cpu()
+    if int(host.min()) < 0 or int(host.max()) >= pool_views:
+        raise ValueError(f"view_schedule holds a value outside [0, {pool_views}): the pool has {pool_views} views")
+    return host.to(torch.int32).contiguous()
 
 
 def _check_lr(lr):
@@ -273,19 +320,37 @@ class SurfelFitter:
     ``ga_fit_accumulate`` joins the captured chain, ``step`` ends a stretch of iterations wherever a clone / split / prune round or
     an opacity reset is due, runs it, and captures the iteration again for the new number of surfels.  ``densify_now()`` runs a round
     at once, ``num_points`` is the present N, ``densify_log`` lists ``(step, N_before, N_after, cloned, split, pruned)`` per round.
+
+    ``visible_only=True``: a surfel whose radius is 0 in every view of an iteration keeps raw, m and v in that iteration.  With view
+    mini-batches "every view" is every view of the batch: a surfel outside every view of the batch keeps raw, m and v.
+
+    ``batch_views=B`` (None: every iteration renders every view, and nothing below exists): view mini-batches.  ``cam_view``,
+    ``cam_view_proj``, ``targets``, ``mask`` and ``normal`` are then a POOL of P >= B views kept on the device (``targets`` may be
+    ``torch.uint8`` in this mode only: the batch receives ``u / 255``), and iteration t renders the B views row t of the view schedule
+    names: ``view_schedule`` (an integer tensor ``[max_steps, B]`` with values in ``[0, P)``, checked here) or, if None,
+    ``fitting.view_schedule(max_steps, P, B, view_seed)``.  The row is selected on the device by the step counter
+    (``ga_fit_select_views``, the first launch of the captured chain), so nothing in an iteration touches the host.  Every internal
+    buffer, loss weight (lambda / B) and densification statistic is that of the batch.  ``set_views`` replaces the pool (same P, H,
+    W), ``set_view_schedule`` the table, neither with a new capture; ``last_views()`` returns the views of the last iteration.  The
+    snapshot / redo path of ``step`` is unchanged: the counter is part of the snapshot, so a redone stretch draws the same rows.  The
+    schedule is configuration, not state: ``state_dict`` does not hold it.
     """
 
     def __init__(self, gaussians, cam_view, cam_view_proj, tanfov, targets, *, mask=None, normal=None, bg=None,
                  l2=0.0, l1=0.8, ssim=0.2, lambda_normal=0.05, lambda_dist=0.0, lambda_alpha=0.0, lr=None,
                  betas=(0.9, 0.999), eps=1e-15, max_steps=DEFAULT_MAX_STEPS, visible_only=False, check_every=50, capacity=None,
-                 densify=None):
+                 densify=None, batch_views=None, view_schedule=None, view_seed=0):
         # ---- everything the host can see is checked before anything is enqueued --------------------------------------------------
         lr = _check_lr(dict(DEFAULT_LR) if lr is None else lr)
         self._densify = _as_config(densify)
         tensors = [("gaussians", gaussians), ("cam_view", cam_view), ("cam_view_proj", cam_view_proj), ("targets", targets)]
         tensors += [(k, t) for k, t in (("mask", mask), ("normal", normal), ("bg", bg)) if t is not None]
+        u8 = isinstance(targets, torch.Tensor) and targets.dtype == torch.uint8
+        if u8 and batch_views is None:
+            raise TypeError("uint8 targets are taken only with batch_views=: the select launch is what converts them")
+        schedule = self._check_minibatch(batch_views, view_schedule, view_seed, targets, max_steps)
         for name, t in tensors:
-            if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            if not isinstance(t, torch.Tensor) or not (t.is_floating_point() or (u8 and name == "targets")):
                 raise TypeError(f"{name} must be a floating-point torch.Tensor")
             if t.device.type != "cuda":
                 raise ValueError(f"{name} is on {t.device}: the fitter only runs on an MI355X (HIP) device; there is no CPU path")
@@ -298,7 +363,11 @@ class SurfelFitter:
             raise ValueError(f"gaussians must be [N,13] or [1,N,13], not {tuple(gaussians.shape)}")
         if targets.dim() != 4 or targets.shape[1] != 3 or targets.numel() == 0:
             raise ValueError(f"targets must be [V,3,H,W], not {tuple(targets.shape)}")
-        self.N, (self.V, _, self.H, self.W) = int(g.shape[0]), (int(x) for x in targets.shape)
+        self.N, (self._P, _, self.H, self.W) = int(g.shape[0]), (int(x) for x in targets.shape)
+        # V: the views of an iteration, what every internal buffer is sized by; P: the views the caller hands over (V without mini-batches)
+        self._batched = schedule is not None
+        self.V = int(batch_views) if self._batched else self._P
+        self._u8 = u8
         self._check_views(cam_view, cam_view_proj, targets, mask, normal)
         if bg is not None and bg.numel() != 3:
             raise ValueError("bg must hold three values")
@@ -335,6 +404,16 @@ class SurfelFitter:
             self._mask = f32(V, 1, H, W) if mask is not None else None
             self._normal = f32(V, 3, H, W) if normal is not None else None
             self._bg = torch.ones(3, dtype=torch.float32, device=dev) if bg is None else bg.detach().float().reshape(3).clone()
+            # what the caller's views are copied into: the buffers the chain reads or, with mini-batches, the pool the select launch reads
+            self._in = {"view": self._view, "proj": self._proj, "targets": self._targets, "mask": self._mask, "normal": self._normal}
+            if self._batched:
+                P = self._P
+                self._in = {"view": f32(P, 16), "proj": f32(P, 16),
+                            "targets": torch.zeros(P, 3, H, W, dtype=torch.uint8 if u8 else torch.float32, device=dev),
+                            "mask": f32(P, 1, H, W) if mask is not None else None,
+                            "normal": f32(P, 3, H, W) if normal is not None else None}
+                self._schedule = schedule.to(dev)
+                self._selected = torch.zeros(V, dtype=torch.int32, device=dev)
             self._copy_views(cam_view, cam_view_proj, targets, mask, normal)
             # rasterizer outputs, the maps of render's differentiable branch and their gradients
             self._color, self._allmap = f32(V, 3, H, W), f32(V, 7, H, W)
@@ -406,13 +485,37 @@ class SurfelFitter:
         return state if self._densify is None else state + (self._grad_accum, self._denom, self._max_radius)
 
     # ---- validation and static inputs ------------------------------------------------------------------------------------------
+    @staticmethod
+    def _check_minibatch(batch_views, view_schedule_, view_seed, targets, max_steps):
+        """-> None without mini-batches, else the view schedule as a host int32 tensor [max_steps, B]: the caller's, checked, or
+        ``view_schedule(max_steps, P, B, view_seed)``"""
+        if batch_views is None:
+            if view_schedule_ is not None:
+                raise ValueError("view_schedule is given without batch_views")
+            return None
+        if not _is_int(batch_views) or batch_views < 1:
+            raise ValueError("batch_views must be None or a positive integer")
+        if not isinstance(targets, torch.Tensor) or targets.dim() != 4:
+            raise ValueError("targets must be [P,3,H,W]")
+        if int(max_steps) < 1:
+            raise ValueError("max_steps and check_every must be at least 1")
+        P = int(targets.shape[0])
+        if batch_views > P:
+            raise ValueError(f"batch_views = {batch_views} exceeds the pool of {P} views")
+        if view_schedule_ is not None:
+            return _check_schedule(view_schedule_, int(max_steps), P, int(batch_views))
+        return view_schedule(int(max_steps), P, int(batch_views), view_seed)
+
     def _check_views(self, cam_view, cam_view_proj, targets, mask, normal):
-        V, H, W = self.V, self.H, self.W
+        V, H, W = self._P, self.H, self.W
         for name, t, shape in (("cam_view", cam_view, (V, 4, 4)), ("cam_view_proj", cam_view_proj, (V, 4, 4)),
                                ("targets", targets, (V, 3, H, W)), ("mask", mask, (V, 1, H, W)), ("normal", normal, (V, 3, H, W))):
             if t is None:
                 continue
-            if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            if name == "targets" and self._u8:
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+                    raise TypeError("targets must be a torch.uint8 tensor: the pool was constructed as one")
+            elif not isinstance(t, torch.Tensor) or not t.is_floating_point():
                 raise TypeError(f"{name} must be a floating-point torch.Tensor")
             if t.device.type != "cuda":
                 raise ValueError(f"{name} is on {t.device}: the fitter only runs on an MI355X (HIP) device; there is no CPU path")
@@ -422,27 +525,48 @@ class SurfelFitter:
                 raise ValueError(f"{name} requires grad: it is a constant of the fit")
 
     def _copy_views(self, cam_view, cam_view_proj, targets, mask, normal):
-        self._view.copy_(cam_view.detach().reshape(self.V, 16))
-        self._proj.copy_(cam_view_proj.detach().reshape(self.V, 16))
-        self._targets.copy_(targets.detach())
+        self._in["view"].copy_(cam_view.detach().reshape(self._P, 16))
+        self._in["proj"].copy_(cam_view_proj.detach().reshape(self._P, 16))
+        self._in["targets"].copy_(targets.detach())
         if mask is not None:
-            self._mask.copy_(mask.detach())
+            self._in["mask"].copy_(mask.detach())
         if normal is not None:
-            self._normal.copy_(normal.detach())
+            self._in["normal"].copy_(normal.detach())
 
     def set_views(self, cam_view, cam_view_proj, targets, mask=None, normal=None):
         """Replace cameras and targets (same V, H, W): copies into the buffers the captured graph reads, no new capture.  ``mask`` /
-        ``normal`` can be replaced only where the fitter was constructed with one."""
+        ``normal`` can be replaced only where the fitter was constructed with one.  With view mini-batches this replaces the pool: the
+        same P, H, W and targets dtype, and the schedule stays."""
         self._check_views(cam_view, cam_view_proj, targets, mask, normal)
         if (mask is not None and self._mask is None) or (normal is not None and self._normal is None):
             raise ValueError("the fitter was constructed without a mask / normal target: the captured graph does not read one")
         self._copy_views(cam_view, cam_view_proj, targets, mask, normal)
+
+    def set_view_schedule(self, view_schedule):
+        """Replace the table of view mini-batches (an integer tensor ``[max_steps, B]`` with values in ``[0, P)``): a copy into the
+        table the captured graph reads, no new capture.  The rows of iterations already taken are not looked at again."""
+        if not self._batched:
+            raise RuntimeError("this fitter was constructed without batch_views=")
+        self._schedule.copy_(_check_schedule(view_schedule, self.max_steps, self._P, self.V))
+
+    def last_views(self) -> torch.Tensor:
+        """[B] int32: the pool views of the last iteration, as ``ga_fit_select_views`` wrote them (a copy)"""
+        if not self._batched:
+            raise RuntimeError("this fitter was constructed without batch_views=")
+        return self._selected.clone()
 
     # ---- the launches ------------------------------------------------------------------------------------------------------------
     def _bind(self):
         """(re)build every argument block but the forward's (``self._fwd`` holds it): after construction and after the workspace has
         grown"""
         N, V, H, W, ws = self.N, self.V, self.H, self.W, self._fwd.ws
+        if self._batched:
+            pool = self._in
+            self._a_sel = _lib.GaFitSelectArgs(
+                self._P, V, H, W, self.max_steps, _lib.GA_FIT_SELECT_U8_TARGETS if self._u8 else 0, self._schedule.data_ptr(),
+                self._counter.data_ptr(), pool["view"].data_ptr(), pool["proj"].data_ptr(), pool["targets"].data_ptr(),
+                _ptr(pool["mask"]), _ptr(pool["normal"]), self._view.data_ptr(), self._proj.data_ptr(), self._targets.data_ptr(),
+                _ptr(self._mask), _ptr(self._normal), self._selected.data_ptr())
         self._a_act = _lib.GaFitActivateArgs(N, 0, self._raw.data_ptr(), self._means.data_ptr(), self._opac.data_ptr(),
                                              self._colors.data_ptr(), self._scales.data_ptr(), self._rots.data_ptr(),
                                              self._inv_norm.data_ptr())
@@ -494,6 +618,8 @@ class SurfelFitter:
         """one iteration on the current stream: a single chain, nothing synchronises"""
         L, ref = self._L, ctypes.byref
         s = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if self._batched:
+            _lib.check(L.ga_fit_select_views(ref(self._a_sel), s), "ga_fit_select_views")
         _lib.check(L.ga_fit_activate(ref(self._a_act), s), "ga_fit_activate")
         self._fwd.run()
         _lib.check(L.ga_surfel_postprocess(ref(self._a_post), s), "ga_surfel_postprocess")

@@ -1,7 +1,8 @@
 /*
  * ga_fit.h -- C-ABI of the glue that turns the surfel rasterizer, its backward and the two device losses into one fitting iteration
  * without a host round trip (csrc/surfel_fit.hip): activation of the raw parameters, the adjoint of the renderer's post-processing,
- * a fused chain-rule + Adam step and the advance of the device-side step counter.
+ * a fused chain-rule + Adam step and the advance of the device-side step counter; and, for fitting against more views than one iteration
+ * renders, the selection of this iteration's views from a pool on the device (ga_fit_select_views).
  *
  * Conventions as in ga_loss.h: device pointers unless marked host, caller owns every buffer, work is enqueued on `stream`, 0 or a
  * negative GA_ERR_* code is returned, nothing synchronises, allocates or reads back.
@@ -121,6 +122,34 @@ typedef struct GaFitAdvanceArgs {
                                 forward; these outlive it, so a host that looks every k iterations misses no overflow              */
 } GaFitAdvanceArgs;
 int ga_fit_advance(const GaFitAdvanceArgs *args, void *stream);
+
+/* View mini-batches.  One launch, the first of the iteration's chain: the B-view buffers the rest of the chain reads are filled from a
+ * pool of P views that stays on the device.  The row of `schedule` is t = clamp(*counter, 0, max_steps - 1) -- the same device word that
+ * selects the Adam table row, so a captured graph draws another row at every replay; ga_fit_advance, the last launch of the chain, is
+ * the only writer, so every reader of the counter in iteration t sees t.  Slot b takes pool view clamp(schedule[t*B + b], 0, P - 1): the
+ * caller validates the table, the clamp only guarantees that no lane reads outside the pool.  A row may name a view twice.
+ * fp32 data are copied bit for bit (NaN payloads, -0, denormals).  With GA_FIT_SELECT_U8_TARGETS pool_targets is uint8 and the batch
+ * receives (float)u / 255.0f, the correctly rounded quotient.  Each lane moves 16 bytes where H*W % 4 == 0 and every pointer below but
+ * schedule, counter and selected is 16-byte aligned, else one element; the grid is capped and strided.
+ * GA_ERR_NULL_ARG: a required pointer is NULL, or mask / normal is given on one side (pool, batch) only.  GA_ERR_BAD_SHAPE: P, B, H, W or
+ * max_steps < 1, B > P, H*W >= 2^31.  GA_ERR_BAD_FLAGS: an unknown flag. */
+#define GA_FIT_SELECT_U8_TARGETS 1
+typedef struct GaFitSelectArgs {
+    int32_t pool_views, batch_views, height, width, max_steps, flags;   /* P, B, H, W                                      */
+    const int32_t *schedule;     /* [max_steps, B]                                                                           */
+    const int32_t *counter;      /* the fitter's device word; read, never written                                            */
+    const float *pool_view;      /* [P,16]                                                                                   */
+    const float *pool_proj;      /* [P,16]                                                                                   */
+    const void *pool_targets;    /* [P,3,H,W] fp32, or uint8 with GA_FIT_SELECT_U8_TARGETS                                   */
+    const float *pool_mask;      /* [P,1,H,W] or NULL                                                                        */
+    const float *pool_normal;    /* [P,3,H,W] or NULL                                                                        */
+    float *view, *proj;          /* [B,16] each                                                                              */
+    float *targets;              /* [B,3,H,W]                                                                                */
+    float *mask;                 /* [B,1,H,W]; NULL exactly where pool_mask is                                               */
+    float *normal;               /* [B,3,H,W]; NULL exactly where pool_normal is                                             */
+    int32_t *selected;           /* [B] or NULL: the pool indices used by this iteration                                     */
+} GaFitSelectArgs;
+int ga_fit_select_views(const GaFitSelectArgs *args, void *stream);
 
 #ifdef __cplusplus
 }
