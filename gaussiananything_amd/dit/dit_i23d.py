@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from .. import dit_ops as ops
+from .device_samplers import DeviceSamplers
 
 
 class _RMSNormW(nn.Module):  # parameter holder: key "<name>.weight"
@@ -152,6 +153,8 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
         """what the host code below keeps per module besides the parameters (every constructor of the family ends with this)"""
         self._pack = None
         self._ctx_cache = None
+        self._pooled_cache = None
+        self._samplers = DeviceSamplers(self)  # resident conditioning and the captured sampler steps; _prepare() drops them with the pack
         self._busy = threading.RLock()        # see _exclusive()
         self._last_use = None                # (stream, event recorded behind the last call's work)
 
@@ -259,6 +262,7 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
         self._pack = dict(sig=sig, device=device, model=model, blocks=blocks, keep=keep, ws=None, ws_key=None)
         self._ctx_cache = None
         self._pooled_cache = None
+        self._samplers.drop()      # the captured sampler steps read the previous pack's weight copies by address
         return self._pack
 
     def invalidate_conditioning_cache(self):
@@ -322,7 +326,7 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
         if not self.pooled_once:
             return None
         key = (vec.data_ptr(), vec._version, tuple(vec.shape))
-        held = getattr(self, "_pooled_cache", None)
+        held = self._pooled_cache
         if held is not None and held[0] == key:
             return held[1]
         B = vec.shape[0]
@@ -388,328 +392,20 @@ class DiT_I23D_PCD_PixelArt_noclip(nn.Module):
         guidance is a no-op (unconditional conditioning == conditional one, the release's stage 2; cascade.sample)."""
         return self.forward(x, t, context)
 
-    def _resident_context(self, context):
-        """The conditioning of a sampling call copied into buffers the model owns (one set per shape): every evaluation of the call --
-        and the captured sampler step, which has their addresses baked in -- reads these, so the step captured for one sample is
-        replayed for the next one (capturing ~1 750 launches costs ~10 ms per call)."""
-        held = getattr(self, "_ctx_bufs", None) or {}
-        out = {}
-        for name, t in context.items():
-            want = torch.float32 if name in (self._vec_key, "fps-xyz") else t.dtype
-            buf = held.get(name)
-            if buf is None or buf.shape != t.shape or buf.dtype != want or buf.device != t.device:
-                buf = torch.empty(t.shape, dtype=want, device=t.device)
-            buf.copy_(t.detach())
-            out[name] = buf
-        self._ctx_bufs = out
-        return out
-
-    def _replay_signature(self, context, shape, n, cfg, cfg_scale):
-        """What a captured sampler step has baked in besides its own buffers: the model's workspace, the K / V projections of the
-        conditioning tokens (refreshed here, in place when the shapes are those of the previous call), the number of batch items
-        that skip the cross-attention, the resident conditioning vectors -- all by address.  None: nothing to replay against yet."""
-        B, L, _ = shape
-        tok = context[self._ctx_key]
-        pack = self._prepare(tok.device)
-        ck, cvt, ca_batch = self._context_kv(pack, tok)
-        if pack.get("ws") is None or pack["ws_key"] != (B, L, tok.shape[1]):
-            return None
-        sig = [tuple(shape), n, bool(cfg), float(cfg_scale), pack["ws"].data_ptr(), ck.data_ptr(), cvt.data_ptr(), ca_batch]
-        vec = context[self._vec_key]
-        if self.pooled_once and vec.dtype == torch.float32 and vec.is_contiguous():
-            sig.append(self._pooled(pack, vec).data_ptr())     # (refreshed in place for this call's vector)
-        for name in (self._vec_key,) + (("fps-xyz",) if self._stage2 else ()):
-            t = context[name]
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                return None   # (forward() would hand the kernels a temporary copy)
-            sig.append((t.data_ptr(), tuple(t.shape)))
-        return tuple(sig)
-
+    # The device-resident samplers: residency of the conditioning, the captured steps held between calls, the rule for replaying one
+    # and the three step bodies live in dit/device_samplers.py (self._samplers); here, the guard around a call on this module
     def sample_euler_fused(self, y0, t_grid, context, cfg_scale=1.0, cfg=True):
         with self._exclusive(y0.device):
-            return self._sample_euler_fused(y0, t_grid, context, cfg_scale, cfg)
-
-    @torch.no_grad()
-    def _sample_euler_fused(self, y0, t_grid, context, cfg_scale=1.0, cfg=True):
-        """The reference's fixed-grid Euler sampling loop (transport/integrators.py:100-119 with method "euler":
-        y_{k+1} = y_k + (t_{k+1} - t_k) f(t_k, y_k), all grid states returned) with the whole step on the device: the
-        function evaluation, the CFG combine of ``forward_with_cfg`` and the state update leave through the final-layer
-        kernel (GaDitSamplerStep), a one-thread kernel moves the step counter / time / step size on, and one step is
-        captured into a HIP graph and replayed -- nothing but this library's kernels between two steps, no host
-        synchronisation.  Bit-identical to the eager loop over ``forward_with_cfg`` / ``forward_cond``."""
-        if self.out_channels != self.in_channels:
-            raise ValueError("the fused sampler step needs a velocity of the state's shape (learn_sigma=False)")
-        dev = y0.device
-        tt = [float(v) for v in t_grid]
-        n = len(tt)
-        context = self._resident_context(context)
-        sig = self._replay_signature(context, y0.shape, n, cfg, cfg_scale) if n >= 2 else None
-        held = getattr(self, "_euler_replay", None)
-        if sig is not None and held is not None and held[0] == sig:     # the step captured by an earlier call, on its buffers
-            _, y, out, t_arr, dt_arr, counter, tvec, dt, step, graph, keep = held
-            out[0].copy_(y0.detach().float())
-            t_arr.copy_(torch.tensor(tt[:-1], dtype=torch.float32))
-            dt_arr.copy_(torch.tensor([b - a for a, b in zip(tt[:-1], tt[1:])], dtype=torch.float32))
-            y.copy_(out[0]); counter.zero_(); tvec.fill_(tt[0]); dt.copy_(dt_arr[0:1])
-            for _ in range(n - 1):
-                graph.replay()
-            return out.clone()
-        y = y0.detach().float().contiguous().clone()
-        out = torch.empty((n,) + tuple(y.shape), dtype=torch.float32, device=dev)
-        out[0].copy_(y)
-        if n < 2:
-            return out
-        B = y.shape[0]
-        t_arr = torch.tensor(tt[:-1], dtype=torch.float32, device=dev)
-        dt_arr = torch.tensor([b - a for a, b in zip(tt[:-1], tt[1:])], dtype=torch.float32, device=dev)
-        counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        tvec = torch.empty(B, dtype=torch.float32, device=dev)
-        dt = torch.empty(1, dtype=torch.float32, device=dev)
-        step = ops.GaDitSamplerStep(float(cfg_scale), 1 if cfg else 0, dt.data_ptr(), y.data_ptr(), out.data_ptr(),
-                                    y.numel(), counter.data_ptr(), None)
-        Lib = ops.lib()
-
-        def one_step():
-            self.forward(y, tvec, context, _step=step)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            ops.check(Lib.ga_dit_sampler_advance(counter.data_ptr(), t_arr.data_ptr(), dt_arr.data_ptr(), n - 1,
-                                                 tvec.data_ptr(), B, dt.data_ptr(), stream), "ga_dit_sampler_advance")
-
-        def reset():
-            y.copy_(out[0])
-            counter.zero_()
-            tvec.fill_(tt[0])
-            dt.copy_(dt_arr[0:1])
-
-        reset()
-        cur = torch.cuda.current_stream(dev)
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):   # warm-up outside the capture: lazy initialisation, workspace sizing, K/V caches
-            one_step()
-        cur.wait_stream(side)
-        reset()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            one_step()
-        reset()   # (capture does not execute; the state is as before)
-        for _ in range(n - 1):
-            graph.replay()
-        # kept for the replays in flight -- and for later calls on the same conditioning tensors (see _replay_signature)
-        sig = self._replay_signature(context, y.shape, n, cfg, cfg_scale)
-        self._euler_replay = (sig, y, out, t_arr, dt_arr, counter, tvec, dt, step, graph, tuple(context.values()))
-        return out.clone() if sig is not None else out
-
+            return self._samplers.euler(y0, t_grid, context, cfg_scale, cfg)
 
     def sample_dopri5_device(self, y0, t_grid, context, cfg_scale=1.0, cfg=True, atol=1e-6, rtol=1e-3, stats=None, max_steps=1 << 16):
         with self._exclusive(y0.device):
-            return self._sample_dopri5_device(y0, t_grid, context, cfg_scale, cfg, atol, rtol, stats, max_steps)
-
-    @torch.no_grad()
-    def _sample_dopri5_device(self, y0, t_grid, context, cfg_scale=1.0, cfg=True, atol=1e-6, rtol=1e-3, stats=None, max_steps=1 << 16):
-        """The reference's DEFAULT sampler -- torchdiffeq's dopri5 behind ``ode.sample`` (transport/integrators.py:100-119,
-        flow_matching_trainer.py:715) -- with the adaptive loop on the device (csrc/ode_dopri5.hip): one attempted step = six
-        (stage input, function evaluation with the guided velocity leaving through the final-layer kernel) pairs, the error norm, a
-        one-thread controller and a predicated accept kernel with the dense output, captured into ONE HIP graph and replayed; time,
-        step size, decisions and counters live in a device block and the host only reads the ``done`` word after a replay.  Same
-        decisions as ``transport/odeint.py`` / ``oracle/ode.py`` (the initial step size is chosen on the host as there: two
-        evaluations).  Returns the states at every requested time."""
-        from ..transport.odeint import _initial_step
-        if self.out_channels != self.in_channels:
-            raise ValueError("the device-resident dopri5 needs a velocity of the state's shape (learn_sigma=False)")
-        dev = y0.device
-        tt = [float(v) for v in t_grid]
-        ng = len(tt)
-        Lib = ops.lib()
-        B, n = y0.shape[0], y0.numel()
-        context = self._resident_context(context)
-        sig = self._replay_signature(context, y0.shape, ng, cfg, cfg_scale)
-        held = getattr(self, "_dopri5_replay", None)
-        if sig is not None and held is not None and held["sig"] == sig:     # buffers and captured step of an earlier call
-            st = held
-        else:
-            y = torch.empty(tuple(y0.shape), dtype=torch.float32, device=dev)
-            st = {"sig": None, "y": y, "out": torch.empty((ng,) + tuple(y.shape), dtype=torch.float32, device=dev),
-                  "k": [torch.empty_like(y) for _ in range(7)], "ystage": torch.empty_like(y),
-                  "tvec": torch.empty(B, dtype=torch.float32, device=dev),
-                  "ctl": torch.zeros(ops.GA_ODE_CTL_ALLOC, dtype=torch.float64, device=dev),
-                  "tg": torch.empty(ng, dtype=torch.float64, device=dev), "graph": None,
-                  "host": torch.empty(ops.GA_ODE_CTL_WORDS, dtype=torch.float64).pin_memory(), "keep": tuple(context.values())}
-        y, out, k, ystage, tvec, ctl, tg, host = (st[q] for q in ("y", "out", "k", "ystage", "tvec", "ctl", "tg", "host"))
-        y.copy_(y0.detach().float())
-        out[0].copy_(y)
-        tg.copy_(torch.tensor(tt, dtype=torch.float64))
-        nfe = [0]
-
-        def velocity_into(dst, x, tv):
-            nfe[0] += 1
-            self.forward(x, tv, context, _step=ops.GaDitSamplerStep(float(cfg_scale), 1 if cfg else 0, None, None, None, 0, None, dst.data_ptr()))
-
-        def rhs(ts, yy):      # (the two host-side evaluations of the initial step size)
-            r = torch.empty_like(y)
-            velocity_into(r, yy.contiguous(), torch.full((B,), float(ts), dtype=torch.float32, device=dev))
-            return r
-
-        tvec.fill_(tt[0])
-        velocity_into(k[0], y, tvec)
-        dt0 = _initial_step(rhs, tt[0], y, k[0], rtol, atol)
-        head = torch.zeros(ops.GA_ODE_CTL_WORDS, dtype=torch.float64)
-        head[ops.GA_ODE_T], head[ops.GA_ODE_DT], head[ops.GA_ODE_ATOL], head[ops.GA_ODE_RTOL], head[ops.GA_ODE_JNEXT] = tt[0], dt0, atol, rtol, 1
-        ctl[:ops.GA_ODE_CTL_WORDS].copy_(head)
-        evals_before = nfe[0]
-        if ng > 1:
-            if st["graph"] is None:
-                ode = ops.GaOdeDopri5(n, B, ng, y.data_ptr(), (ops.c_p * 7)(*[t.data_ptr() for t in k]), ystage.data_ptr(), tvec.data_ptr(),
-                                      ctl.data_ptr(), tg.data_ptr(), out.data_ptr(), ctl.numel())
-
-                def attempt():
-                    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                    for i in range(6):
-                        ops.check(Lib.ga_ode_dopri5_stage(ctypes.byref(ode), i, stream), "ga_ode_dopri5_stage")
-                        velocity_into(k[i + 1], ystage, tvec)
-                    ops.check(Lib.ga_ode_dopri5_finish(ctypes.byref(ode), stream), "ga_ode_dopri5_finish")
-
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):     # (capture executes nothing; the evaluations above were the warm-up)
-                    attempt()
-                st["graph"], st["ode"] = graph, ode
-                nfe[0] = evals_before
-                # (the signature exists once the first evaluations have sized the workspace and cached the K / V)
-                st["sig"] = self._replay_signature(context, y.shape, ng, cfg, cfg_scale)
-                self._dopri5_replay = st
-            graph = st["graph"]
-            done_evt = torch.cuda.Event()
-            while True:
-                graph.replay()
-                host.copy_(ctl[:ops.GA_ODE_CTL_WORDS], non_blocking=True)
-                done_evt.record()
-                done_evt.synchronize()
-                if host[ops.GA_ODE_DONE] != 0 or host[ops.GA_ODE_STEPS] >= max_steps:
-                    break
-            err, steps = int(host[ops.GA_ODE_ERROR]), int(host[ops.GA_ODE_STEPS])
-            if err == 1:
-                raise FloatingPointError(f"dopri5: non-finite error ratio at t = {float(host[ops.GA_ODE_T])}: the model returned NaN/inf")
-            if err == 2:
-                raise FloatingPointError(f"dopri5: step size underflow at t = {float(host[ops.GA_ODE_T])}")
-            if host[ops.GA_ODE_DONE] == 0:
-                raise RuntimeError(f"dopri5: more than {max_steps} attempted steps")
-            if stats is not None:
-                stats.update(nfe=evals_before + 6 * steps, steps=steps, rejected=int(host[ops.GA_ODE_REJECTED]), graph=True, device_loop=True,
-                             ctl=[float(v) for v in host])     # the controller's scalar block after the last step (tests: bit-reproducible)
-        elif stats is not None:
-            stats.update(nfe=evals_before, steps=0, rejected=0, graph=True, device_loop=True)
-        return out.clone()
+            return self._samplers.dopri5(y0, t_grid, context, cfg_scale, cfg, atol, rtol, stats, max_steps)
 
     def sample_sde_device(self, x0, coef, context, method="Euler", last_step="Mean", cfg_scale=1.0, cfg=True, seed=0, noise=None,
                           noise_out=None):
         with self._exclusive(x0.device):
-            return self._sample_sde_device(x0, coef, context, method, last_step, cfg_scale, cfg, seed, noise, noise_out)
-
-    @torch.no_grad()
-    def _sample_sde_device(self, x0, coef, context, method, last_step, cfg_scale, cfg, seed, noise, noise_out):
-        """The reference's SDE sampling loop (``Sampler.sample_sde``, transport/transport.py:322-382: the stepper of
-        transport/integrators.py:8-75 and one last step) with every step on the device (csrc/ode_sde.hip, GaSdeStep in
-        include/ga_dit.h): a step is the function evaluation with the guided velocity leaving through the final-layer kernel, the
-        Euler-Maruyama update (``method="Euler"``) or Heun's three phases around two evaluations (``"Heun"``) with the noise drawn
-        inside the kernel, and the one-thread advance -- captured into ONE HIP graph and replayed for every interval, then the last
-        step eagerly.  The step index, the coefficient table ``coef`` ([intervals + 1, GA_SDE_COEF_STRIDE] fp32, built by
-        ``transport.sampler.sde_coefficients``), the seed and the initial state are device data rewritten per call: the captured step
-        serves any seed, diffusion form and norm, and every replay draws fresh noise.  ``cfg``: the state is a doubled CFG batch whose
-        halves take the same noise.  ``noise`` [intervals, n_draw]: normals to use instead; ``noise_out`` [intervals, n_draw]: receives
-        the normals every step used.  Returns [intervals + 1, *x0.shape] fp32: slot k is the state after step k, the last slot the
-        last step's output.  Bit-identical to the eager loop of ``transport/sampler.py`` on the same normals."""
-        if self.out_channels != self.in_channels:
-            raise ValueError("the device-resident SDE sampler needs a velocity of the state's shape (learn_sigma=False)")
-        phases = {"Euler": (ops.GA_SDE_EM,), "Heun": (ops.GA_SDE_HEUN_PERTURB, ops.GA_SDE_HEUN_PREDICT, ops.GA_SDE_HEUN_CORRECT)}
-        lasts = {"Mean": ops.GA_SDE_LAST_MEAN, "Tweedie": ops.GA_SDE_LAST_TWEEDIE, "Euler": ops.GA_SDE_LAST_EULER, None: ops.GA_SDE_LAST_NONE}
-        if method not in phases or last_step not in lasts:
-            raise ValueError(f"SDE sampler: method {method!r} / last step {last_step!r} (have {tuple(phases)} / {tuple(lasts)})")
-        dev = x0.device
-        ni = coef.shape[0] - 1
-        if coef.dim() != 2 or coef.shape[1] != ops.GA_SDE_COEF_STRIDE or ni < 1:
-            raise ValueError("coef is the [intervals + 1, GA_SDE_COEF_STRIDE] table of sde_coefficients")
-        B, n = x0.shape[0], x0.numel()
-        nd = n // 2 if cfg else n
-        if cfg and B % 2:
-            raise ValueError("a CFG state holds the conditional and the unconditional half")
-        for name, t in (("noise", noise), ("noise_out", noise_out)):
-            if t is not None and (t.numel() != ni * nd or t.shape[0] != ni):
-                raise ValueError(f"{name} is [intervals = {ni}, n_draw = {nd}]")
-        Lib = ops.lib()
-        context = self._resident_context(context)
-        key = (method, ni + 1, noise is not None, noise_out is not None)
-        sig = self._replay_signature(context, x0.shape, ni + 1, cfg, cfg_scale)
-        held = getattr(self, "_sde_replay", None)
-        if sig is not None and held is not None and held["sig"] == (sig, key):     # buffers and captured step of an earlier call
-            st = held
-        else:
-            y = torch.empty(tuple(x0.shape), dtype=torch.float32, device=dev)
-            st = {"sig": None, "y": y, "vel": torch.empty_like(y), "k1": torch.empty_like(y), "xhat": torch.empty_like(y),
-                  "out": torch.empty((ni + 1,) + tuple(y.shape), dtype=torch.float32, device=dev),
-                  "counter": torch.zeros(1, dtype=torch.int32, device=dev), "tvec": torch.empty(B, dtype=torch.float32, device=dev),
-                  "coef": torch.empty((ni + 1, ops.GA_SDE_COEF_STRIDE), dtype=torch.float32, device=dev),
-                  "seed": torch.zeros(1, dtype=torch.int64, device=dev),
-                  "noise": torch.empty((ni, nd), dtype=torch.float32, device=dev) if noise is not None else None,
-                  "nout": torch.empty(nd, dtype=torch.float32, device=dev) if noise_out is not None else None,
-                  "graph": None, "keep": tuple(context.values())}
-        y, vel, out, counter, tvec, cf = (st[q] for q in ("y", "vel", "out", "counter", "tvec", "coef"))
-        cf.copy_(coef.detach().to(torch.float32))
-        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        st["seed"].copy_(torch.tensor([seed - (1 << 64) if seed >> 63 else seed], dtype=torch.int64))
-        if noise is not None:
-            st["noise"].copy_(noise.detach().reshape(ni, nd))
-        sde = ops.GaSdeStep(n, B, ni, 1 if cfg else 0, y.data_ptr(), vel.data_ptr(), st["k1"].data_ptr(), st["xhat"].data_ptr(),
-                            out.data_ptr(), counter.data_ptr(), tvec.data_ptr(), cf.data_ptr(), st["seed"].data_ptr(),
-                            st["noise"].data_ptr() if noise is not None else None, st["nout"].data_ptr() if noise_out is not None else None)
-        vstep = ops.GaDitSamplerStep(float(cfg_scale), 1 if cfg else 0, None, None, None, 0, None, vel.data_ptr())
-
-        def phase(p):
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            ops.check(Lib.ga_sde_step(ctypes.byref(sde), p, stream), "ga_sde_step")
-
-        def one_step():     # a single chain of launches
-            if method == "Euler":
-                self.forward(y, tvec, context, _step=vstep)
-                phase(ops.GA_SDE_EM)
-            else:
-                phase(ops.GA_SDE_HEUN_PERTURB)
-                self.forward(st["xhat"], tvec, context, _step=vstep)
-                phase(ops.GA_SDE_HEUN_PREDICT)
-                self.forward(y, tvec, context, _step=vstep)
-                phase(ops.GA_SDE_HEUN_CORRECT)
-            phase(ops.GA_SDE_ADVANCE)
-
-        def reset():
-            y.copy_(x0.detach().float())
-            counter.zero_()
-            tvec.copy_(cf[0, ops.GA_SDE_C_T].expand(B))
-
-        reset()
-        if st["graph"] is None:
-            cur = torch.cuda.current_stream(dev)
-            side = torch.cuda.Stream(dev)
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):   # warm-up outside the capture: lazy initialisation, workspace sizing, K/V caches
-                one_step()
-            cur.wait_stream(side)
-            reset()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                one_step()
-            reset()   # (capture does not execute; the state is as before)
-            st["graph"] = graph
-            # (the signature exists once the first evaluation has sized the workspace and cached the K / V)
-            sig = self._replay_signature(context, y.shape, ni + 1, cfg, cfg_scale)
-            st["sig"] = (sig, key) if sig is not None else None
-            self._sde_replay = st
-        for k in range(ni):
-            st["graph"].replay()
-            if noise_out is not None:
-                noise_out[k].reshape(-1).copy_(st["nout"])
-        if last_step is not None:
-            self.forward(y, tvec, context, _step=vstep)      # (ADVANCE left t1 in tvec)
-        phase(lasts[last_step])
-        return out.clone()
+            return self._samplers.sde(x0, coef, context, method, last_step, cfg_scale, cfg, seed, noise, noise_out)
 
 
 class DiT_I23D_PCD_PixelArt_noclip_clay_stage2(DiT_I23D_PCD_PixelArt_noclip):
@@ -721,7 +417,7 @@ class DiT_I23D_PCD_PixelArt_noclip_clay_stage2(DiT_I23D_PCD_PixelArt_noclip):
         super().__init__(*args, _stage2=True, **kwargs)
         self.use_pe_cond = use_pe_cond
         self.xyz_pos_embed = _XYZPosEmbed(self.embed_dim)
-        self._pack = None
+        self._init_runtime_state()
 
 
 def _clay(depth, hidden, heads, stage2=False):

@@ -109,7 +109,7 @@ class DiT_PCD_PixelArt_tofeat(DiT_PCD_PixelArt):
         self.xyz_pos_embed = _XYZPosEmbed(self.embed_dim)
         nn.init.xavier_uniform_(self.xyz_pos_embed.xyz_projection.weight)
         nn.init.constant_(self.xyz_pos_embed.xyz_projection.bias, 0)
-        self._pack = None
+        self._init_runtime_state()
 
 
 def _pcd(depth, hidden, heads, stage2=False):

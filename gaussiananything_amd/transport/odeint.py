@@ -65,6 +65,28 @@ _C_MID = [6025192743 / 30085553152 / 2, 0, 51252292925 / 65400821598 / 2, -26918
 _EVALS = {"euler": 1, "midpoint": 2, "heun2": 2, "heun3": 3, "rk4": 4}
 
 
+def capture_step(step, reset, dev, warm_up=True):
+    """``step()`` captured into a HIP graph: the one place a sampler step is captured (the fixed grid below, the device-resident
+    samplers of dit/device_samplers.py).  ``reset()`` puts the state ``step`` advances back to its start.  With ``warm_up`` the
+    step first runs once outside the capture, on a side stream that waits for the current one -- lazy initialisation, workspace
+    sizing, K/V caches; a caller whose own evaluations have done all that switches it off and has nothing to reset."""
+    if warm_up:
+        cur = torch.cuda.current_stream(dev)
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            reset()
+            step()
+        cur.wait_stream(side)
+        reset()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        step()
+    if warm_up:
+        reset()   # (capture does not execute; the state is as before)
+    return graph
+
+
 def _fixed_grid_graph(method, func, y, tt, out):
     """Fixed-grid integration with ONE step captured into a HIP graph and replayed per grid interval.
 
@@ -82,17 +104,12 @@ def _fixed_grid_graph(method, func, y, tt, out):
     def ff(ts, yy):
         return func(ts, yy).float()
 
-    cur = torch.cuda.current_stream(dev)
-    side = torch.cuda.Stream(dev)
-    side.wait_stream(cur)
-    with torch.cuda.stream(side):  # warm-up outside the capture: lazy initialisation, workspace sizing, K/V caches
+    def reset():
         t_cur.copy_(t_dev[0])
         dt_cur.copy_(dt_dev[0])
-        _rk_fixed(method, ff, t_cur, dt_cur, t_cur + dt_cur, y_st)
-    cur.wait_stream(side)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        y_st.add_(_rk_fixed(method, ff, t_cur, dt_cur, t_cur + dt_cur, y_st))
+        y_st.copy_(y)
+
+    graph = capture_step(lambda: y_st.add_(_rk_fixed(method, ff, t_cur, dt_cur, t_cur + dt_cur, y_st)), reset, dev)
     for j in range(1, len(tt)):
         t_cur.copy_(t_dev[j - 1])
         dt_cur.copy_(dt_dev[j - 1])

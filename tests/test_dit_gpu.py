@@ -924,13 +924,13 @@ def test_device_resident_dopri5_takes_the_decisions_of_the_host_loop(gpu_device,
         assert torch.equal(b[0], x.float())
         # a second call on the same conditioning tensors replays the step captured by the first (no new capture), on another start
         # state; the first result is not overwritten
-        held = model._dopri5_replay["graph"]
+        held = model._samplers.held("dopri5").graph
         keep = b.clone()
         fn = sampler.sample_ode(sampling_method="dopri5", num_steps=n_out, atol=1e-6, rtol=1e-3)
         with torch.no_grad():
             again = fn(x, fwd, context=ctx, cfg_scale=z["cfg_scale"])
             other = fn(0.5 * x, fwd, context=ctx, cfg_scale=z["cfg_scale"])
-        assert model._dopri5_replay["graph"] is held and torch.equal(again, keep) and torch.equal(b, keep)
+        assert model._samplers.held("dopri5").graph is held and torch.equal(again, keep) and torch.equal(b, keep)
         assert not torch.equal(other[-1], keep[-1]) and torch.equal(other[0], 0.5 * x.float())
 
 
@@ -1100,13 +1100,87 @@ def test_sampler_graph_replay_equals_eager_loop(gpu_device, method, monkeypatch)
     if method == "euler":
         assert torch.equal(outs["0"], outs["1"])
         assert sampler.last_ode.last_stats.get("fused")      # the on-device step (GaDitSamplerStep) was the one replayed
-        held = model._euler_replay[9]                        # a second call on the same conditioning replays the captured step
+        held = model._samplers.held("euler").graph                  # a second call on the same conditioning replays the captured step
         with torch.no_grad():
             again = fn(x, model.forward_with_cfg, context=ctx, cfg_scale=z["cfg_scale"])
             other = fn(2.0 * x, model.forward_with_cfg, context=ctx, cfg_scale=z["cfg_scale"])
-        assert model._euler_replay[9] is held and torch.equal(again, outs["1"]) and not torch.equal(other[-1], again[-1])
+        assert model._samplers.held("euler").graph is held and torch.equal(again, outs["1"]) and not torch.equal(other[-1], again[-1])
     else:
         assert rel_l2(outs["1"], outs["0"]) < 1e-5
+
+
+def _three_sampler_kinds(model, z, ctx, device):
+    """the three device-resident samplers on the stage-1 golden (CFG state [4, 48, 3]): kind -> call returning (states, dopri5's ctl block)"""
+    from gaussiananything_amd.transport import Sampler, create_transport
+    sampler = Sampler(create_transport("GVP", "velocity", None, None, None, snr_type="uniform"))
+    x = z["x"].to(device)
+    assert tuple(x.shape) == (4, 48, 3)
+    pairs = torch.cat([x[:2], x[:2]], 0)
+    kw = dict(context=ctx, cfg_scale=z["cfg_scale"])
+
+    def euler():
+        return sampler.sample_ode(sampling_method="euler", num_steps=7)(x, model.forward_with_cfg, **kw), None
+
+    def dopri5():
+        out = sampler.sample_ode(sampling_method="dopri5", num_steps=9, atol=1e-6, rtol=1e-3)(x, model.forward_with_cfg, **kw)
+        assert sampler.last_ode.last_stats.get("device_loop")
+        return out, list(sampler.last_ode.last_stats["ctl"])
+
+    def sde():
+        out = sampler.sample_sde(num_steps=7, seed=5)(pairs, model.forward_with_cfg, **kw)
+        assert sampler.last_sde.last_stats.get("fused") is True
+        return out, None
+
+    return {"euler": euler, "dopri5": dopri5, "sde": sde}
+
+
+def test_interleaved_sampler_kinds_keep_their_held_steps(gpu_device):
+    """Euler, dopri5 and the SDE sampler called in turn on one module, then again in another order: a call of one kind does not evict the
+    captured step of another (the same graph object serves both rounds), and every second result is the first one's, bit for bit."""
+    z, model, ctx = _load_golden(1, gpu_device)
+    calls = _three_sampler_kinds(model, z, ctx, gpu_device)
+    first, graphs = {}, {}
+    with torch.no_grad():
+        for kind in ("euler", "dopri5", "sde"):
+            first[kind] = calls[kind]()
+            graphs[kind] = model._samplers.held(kind).graph
+        assert all(g is not None for g in graphs.values())
+        for kind in ("sde", "euler", "dopri5"):
+            out, ctl = calls[kind]()
+            assert model._samplers.held(kind).graph is graphs[kind], kind
+            assert torch.equal(out, first[kind][0]), kind
+            assert ctl == first[kind][1], kind
+    assert len(first["dopri5"][1]) > 0
+    assert all(model._samplers.held(kind).graph is graphs[kind] for kind in graphs)
+
+
+def test_a_weight_change_drops_the_held_sampler_steps(gpu_device):
+    """A step captured for one weight pack has that pack's weight copies baked in by address: after an in-place weight change every
+    kind captures anew, and computes what a freshly constructed module with the changed weights computes -- not what it did before."""
+    from gaussiananything_amd.dit import DiT_I23D_PCD_PixelArt_noclip
+    z, model, ctx = _load_golden(1, gpu_device)
+    calls = _three_sampler_kinds(model, z, ctx, gpu_device)
+    kinds = ("euler", "dopri5", "sde")
+    with torch.no_grad():
+        before = {kind: calls[kind]() for kind in kinds}
+        graphs = {kind: model._samplers.held(kind).graph for kind in kinds}
+        assert all(g is not None for g in graphs.values())
+        w = model.blocks[0].mlp.mlp[2].weight          # fc2 of the first block: non-zero in the golden
+        assert float(w.abs().max()) > 0.0
+        w.mul_(1.5)
+        after = {}
+        for kind in kinds:
+            after[kind] = calls[kind]()
+            assert model._samplers.held(kind).graph is not None and model._samplers.held(kind).graph is not graphs[kind], kind
+        fresh = DiT_I23D_PCD_PixelArt_noclip(**z["kwargs"])
+        fresh.load_state_dict(model.state_dict(), strict=True)
+        fresh.to(gpu_device)
+        want = {kind: call() for kind, call in _three_sampler_kinds(fresh, z, ctx, gpu_device).items()}
+    for kind in kinds:
+        assert torch.equal(after[kind][0], want[kind][0]), kind
+        assert after[kind][1] == want[kind][1], kind
+        assert not torch.equal(after[kind][0], before[kind][0]), kind
+    assert len(after["dopri5"][1]) > 0
 
 
 @pytest.mark.parametrize("stage", [1, 2])

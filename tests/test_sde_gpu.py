@@ -227,11 +227,11 @@ def test_g4_replay_draws_fresh_noise_and_the_cache_serves_any_seed(gpu_device):
     call = lambda seed: _sampler().sample_sde(num_steps=7, seed=seed)(x0, model.forward_with_cfg, context=ctx,   # noqa: E731
                                                                       cfg_scale=z["cfg_scale"])
     a = call(77)
-    graph = model._sde_replay["graph"]
+    graph = model._samplers.held("sde").graph
     b = call(77)
-    assert model._sde_replay["graph"] is graph
+    assert model._samplers.held("sde").graph is graph
     c = call(78)
-    assert model._sde_replay["graph"] is graph                          # the seed is device data: no re-capture
+    assert model._samplers.held("sde").graph is graph                          # the seed is device data: no re-capture
     assert torch.equal(a.view(torch.int32), b.view(torch.int32)) and not torch.equal(a, c)
     assert torch.equal(a[:, :2], a[:, 2:]) and bool(a.isfinite().all())
     worst = 0.0
