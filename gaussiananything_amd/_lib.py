@@ -125,6 +125,27 @@ class GaKnnBackwardArgs(ctypes.Structure):
                 ("grad_query", ctypes.c_void_p), ("grad_target", ctypes.c_void_p)]
 
 
+class GaNormalsArgs(ctypes.Structure):
+    """include/ga_pointcloud.h: GaNormalsArgs"""
+    _fields_ = [("batch", ctypes.c_int32), ("num_points", ctypes.c_int32), ("k", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("points", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("idx", ctypes.c_void_p), ("viewpoint", ctypes.c_void_p),
+                ("normal", ctypes.c_void_p), ("tangent", ctypes.c_void_p), ("eigenvalues", ctypes.c_void_p)]
+
+
+class GaNormalsPlan(ctypes.Structure):
+    """include/ga_pointcloud.h: GaNormalsPlan"""
+    _fields_ = [("threads", ctypes.c_int32), ("grid_x", ctypes.c_int32), ("grid_y", ctypes.c_int32), ("sweeps", ctypes.c_int32)]
+
+
+class GaSurfelInitArgs(ctypes.Structure):
+    """include/ga_pointcloud.h: GaSurfelInitArgs"""
+    _fields_ = [("batch", ctypes.c_int32), ("num_points", ctypes.c_int32), ("k", ctypes.c_int32), ("opacity", ctypes.c_float),
+                ("scale_factor", ctypes.c_float), ("reserved", ctypes.c_int32),
+                ("points", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("tangent", ctypes.c_void_p), ("dist2", ctypes.c_void_p),
+                ("lengths", ctypes.c_void_p), ("eigenvalues", ctypes.c_void_p), ("colors", ctypes.c_void_p),
+                ("gaussians", ctypes.c_void_p)]
+
+
 class GaPhotoLossArgs(ctypes.Structure):
     """include/ga_loss.h: GaPhotoLossArgs"""
     _fields_ = [("num_images", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
@@ -227,12 +248,13 @@ GA_FPS_VARIANT_REGISTER, GA_FPS_VARIANT_STREAMING = 0, 1
 GA_PHOTO_LOSS_SAVE = 1
 GA_GEO_LOSS_TARGET, GA_GEO_LOSS_NORMALS = 1, 2
 GA_PC_KNN_MAX_K = 32
+GA_PC_NORMALS_SWEEPS, GA_PC_NORMALS_MIN_K, GA_PC_SURFEL_MIN_K, GA_PC_SURFEL_FLOATS = 5, 3, 4, 13
 
 EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspace_layout2", "ga_surfel_forward", "ga_surfel_postprocess",
            "ga_surfel_backward", "ga_surfel_backward_scratch_bytes", "ga_surfel_store_policy",
            "ga_tsdf_integrate", "ga_tsdf_mesh_scratch_bytes", "ga_tsdf_mesh_count", "ga_tsdf_mesh_emit", "ga_mesh_write_obj", "ga_mesh_cluster_labels",
            "ga_pc_fps", "ga_pc_fps_plan", "ga_pc_fps_workspace_bytes", "ga_pc_nearest",
-           "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward",
+           "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward", "ga_pc_normals", "ga_pc_normals_plan", "ga_pc_surfel_init",
            "ga_photo_loss_plan", "ga_photo_loss_workspace_bytes", "ga_photo_loss_forward", "ga_photo_loss_backward",
            "ga_geo_loss_plan", "ga_geo_loss_workspace_bytes", "ga_geo_loss_forward", "ga_geo_loss_backward",
            "ga_fit_plan", "ga_fit_activate", "ga_fit_pack_grads", "ga_fit_adam", "ga_fit_advance", "ga_fit_select_views",
@@ -308,6 +330,12 @@ def lib():
         L.ga_pc_knn_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GaKnnPlan)]
         L.ga_pc_knn_backward.restype = ctypes.c_int
         L.ga_pc_knn_backward.argtypes = [ctypes.POINTER(GaKnnBackwardArgs), ctypes.c_void_p]
+        L.ga_pc_normals.restype = ctypes.c_int
+        L.ga_pc_normals.argtypes = [ctypes.POINTER(GaNormalsArgs), ctypes.c_void_p]
+        L.ga_pc_normals_plan.restype = ctypes.c_int
+        L.ga_pc_normals_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GaNormalsPlan)]
+        L.ga_pc_surfel_init.restype = ctypes.c_int
+        L.ga_pc_surfel_init.argtypes = [ctypes.POINTER(GaSurfelInitArgs), ctypes.c_void_p]
         L.ga_photo_loss_plan.restype = ctypes.c_int
         L.ga_photo_loss_plan.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(GaPhotoLossPlan)]
         L.ga_photo_loss_workspace_bytes.restype = ctypes.c_size_t

@@ -2,6 +2,7 @@
 csrc/surfel_fit.hip and csrc/surfel_densify.hip).
 
     to_raw           the inverse of the activation: a Gaussian tensor [N,13] -> the raw parameters the optimiser moves
+    surfels_from_points   a point cloud -> the Gaussian tensor [N,13] a fit can start from (``SurfelFitter.from_points`` wraps it)
     step_table       the per-step Adam step sizes and bias corrections, computed in double, stored fp32
     view_schedule    the table of view mini-batches: which views of a pool every iteration renders (epochs of random permutations)
     SurfelFitter     one iteration = ga_fit_activate -> ga_surfel_forward -> post-processing -> the two loss forwards -> the two loss
@@ -61,6 +62,31 @@ def to_raw(gaussians: torch.Tensor) -> torch.Tensor:
     p = torch.cat([g[:, 3:4], g[:, 10:13]], dim=1).clamp(1e-6, 1 - 1e-6)
     logit = torch.log(p) - torch.log1p(-p)
     return torch.cat([g[:, 0:3], logit[:, 0:1], torch.log(g[:, 4:6].clamp_min(1e-8)), g[:, 6:10], logit[:, 1:4]], dim=1).contiguous()
+
+
+def surfels_from_points(points, colors=None, normals=None, K=16, opacity=0.1, scale_factor=1.0) -> torch.Tensor:
+    """A point cloud [N,3] or [1,N,3] (SfM points, a scan, a stage-1 cloud) -> activated surfels [N,13] fp32 on its device, what
+    ``SurfelFitter`` and ``to_raw`` take: the disc of every point lies in the plane PCA fits to its ``K`` nearest points (or is
+    perpendicular to ``normals`` [N,3] when given), its two scales are ``scale_factor`` times the root mean squared distance to the
+    three nearest other points (2DGS's ``create_from_pcd`` rule; 2DGS draws the rotations at random), its opacity ``opacity``, its
+    colour ``colors`` [N,3] in [0, 1] or 0.5.  ``pointcloud.surfels_from_cloud`` on a batch of one: the kNN launch and two
+    per-point launches, no host read.  A point whose neighbours all coincide with it gets opacity 0 (``pointcloud.estimate_normals``).
+    Not built: anisotropic initial scales, SH colours, orientation propagation, unprojecting RGB-D views to points."""
+    from . import pointcloud
+
+    def batched(t, name):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+            raise TypeError(f"{name} must be a floating-point torch.Tensor")
+        if t.dim() == 2:
+            t = t[None]
+        if t.dim() != 3 or t.shape[0] != 1 or t.shape[2] != 3 or t.shape[1] < 1:
+            raise ValueError(f"{name} must be [N,3] or [1,N,3], not {tuple(t.shape)}")
+        return t
+
+    p, c, n = batched(points, "points"), batched(colors, "colors"), batched(normals, "normals")
+    return pointcloud.surfels_from_cloud(p, None, c, n, K, opacity, scale_factor)[0]
 
 
 def _lr_at(spec, t, max_steps):
@@ -440,6 +466,14 @@ class SurfelFitter:
             self._allocate_points(raw, None, None, int(capacity) if capacity is not None else default_capacity(N, V))
             self._bind()
             self._warm_up_and_capture()
+
+    @classmethod
+    def from_points(cls, points, cam_view, cam_view_proj, tanfov, targets, *, colors=None, normals=None, K=16, opacity=0.1,
+                    scale_factor=1.0, **fitter_kwargs):
+        """A fitter that starts from a point cloud [N,3] or [1,N,3] instead of finished Gaussians: ``surfels_from_points(points, colors,
+        normals, K, opacity, scale_factor)`` and then the constructor with ``fitter_kwargs``."""
+        g = surfels_from_points(points, colors=colors, normals=normals, K=K, opacity=opacity, scale_factor=scale_factor)
+        return cls(g, cam_view, cam_view_proj, tanfov, targets, **fitter_kwargs)
 
     def _allocate_points(self, raw, m, v, capacity, seg_capacity=0):
         """everything whose size depends on the number of surfels: the state and its snapshot, the activated arrays, the radii, the

@@ -241,6 +241,50 @@ def load_colored_points_ply(path):
             np.stack([rec["red"], rec["green"], rec["blue"], rec["alpha"]], 1).copy())
 
 
+_ORIENTED = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+_RGB = [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+
+
+def save_oriented_points_ply(path, xyz, normals, colors=None):
+    """Vertex-only binary little-endian PLY with float32 ``x y z nx ny nz`` and, with ``colors`` ([N,3] floats in [0, 1] or uint8),
+    uchar ``red green blue``: what an oriented-point reader (a Poisson reconstruction tool, meshlab) takes.  The floats are written
+    bit for bit."""
+    v = np.asarray(xyz, dtype="<f4").reshape(-1, 3)
+    n = np.asarray(normals, dtype="<f4").reshape(-1, 3)
+    if n.shape != v.shape:
+        raise ValueError(f"normals must be [{v.shape[0]}, 3], got {tuple(n.shape)}")
+    rec = np.empty(v.shape[0], dtype=_ORIENTED + (_RGB if colors is not None else []))
+    for k, name in enumerate("xyz"):
+        rec[name], rec["n" + name] = v[:, k], n[:, k]
+    if colors is not None:
+        c = colors_to_rgba8(colors, v.shape[0])
+        rec["red"], rec["green"], rec["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    header = ("ply\nformat binary_little_endian 1.0\n" + f"element vertex {v.shape[0]}\n" +
+              "".join(f"property float {name}\n" for name, _ in _ORIENTED) +
+              ("".join(f"property uchar {name}\n" for name, _ in _RGB) if colors is not None else "") + "end_header\n")
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def load_oriented_points_ply(path):
+    """-> (xyz [N,3] f32, normals [N,3] f32, rgb [N,3] u8 or None) of a file written by ``save_oriented_points_ply``."""
+    with open(path, "rb") as f:
+        data = f.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").splitlines()
+    if lines[0].strip() != "ply" or "format binary_little_endian 1.0" not in lines:
+        raise ValueError(f"{path}: not a binary little-endian PLY file")
+    n = next(int(l.split()[2]) for l in lines if l.startswith("element vertex"))
+    names = [l.split()[2] for l in lines if l.startswith("property")]
+    plain, coloured = [k for k, _ in _ORIENTED], [k for k, _ in _ORIENTED + _RGB]
+    if names not in (plain, coloured):
+        raise ValueError(f"{path}: the vertex properties are {names}, not x y z nx ny nz [red green blue]")
+    rec = np.frombuffer(data, dtype=np.dtype(_ORIENTED + (_RGB if names == coloured else [])), count=n, offset=end)
+    return (np.stack([rec["x"], rec["y"], rec["z"]], 1).copy(), np.stack([rec["nx"], rec["ny"], rec["nz"]], 1).copy(),
+            np.stack([rec["red"], rec["green"], rec["blue"]], 1).copy() if names == coloured else None)
+
+
 def export_gaussian_point_cloud(fine_gs, output_dir, name_prefix):
     """What the engine leaves beside a decoded sample (flow_matching_trainer.py:1452-1475): the surfel centres, turned for the
     viewer (``R_x(-90 deg)`` applied to the points, then ``@ R_y(pi).T``), coloured with the surfel rgb, as

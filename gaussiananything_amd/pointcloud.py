@@ -10,6 +10,10 @@
                              with gradients through ``ga_pc_knn_backward``
     remove_statistical_outliers   mean distance to the k nearest neighbours against the cloud's mean + ratio * deviation: OUR OWN
                              definition, parity with Open3D's filter of the same name is not claimed
+    estimate_normals         PCA normals (and tangents, eigenvalues) from the k nearest neighbours, ``ga_pc_normals`` (csrc/pc_normals.hip):
+                             OUR OWN definition, sign and invalid-row rules included
+    surfels_from_cloud       initial 2D surfels [B,N,13] from a cloud, ``ga_pc_surfel_init``: 2DGS's distance rule for the scale, the
+                             PCA frame for the rotation (``fitting.surfels_from_points`` is the single-cloud front end)
 
 pytorch3d is absent from this image; its published behaviour is restated, parity UNPINNED ('Point clouds').  The tensors
 stay on the device and the work goes on the current stream.  There is no CPU fallback: without the HIP library, or on a CPU tensor,
@@ -311,3 +315,91 @@ def remove_statistical_outliers(points: torch.Tensor, lengths=None, nb_neighbors
     order = torch.argsort((~keep).to(torch.uint8), dim=1, stable=True)                               # kept first, original order
     out = p.gather(1, order[:, :, None].expand(-1, -1, 3)) * keep.gather(1, order)[:, :, None]
     return out, keep.sum(1), keep
+
+
+# ---- normals and the surfel initialiser (include/ga_pointcloud.h, csrc/pc_normals.hip) ------------------------------------------------
+def normals_plan(num_points: int, K: int = 16) -> dict:
+    """What ``ga_pc_normals`` launches: {'threads', 'grid_x', 'grid_y', 'sweeps'} (the grid is grid_x by grid_y * B)."""
+    pl = _lib.GaNormalsPlan()
+    _lib.check(_lib.lib().ga_pc_normals_plan(int(num_points), int(K), ctypes.byref(pl)), "ga_pc_normals_plan")
+    return {"threads": pl.threads, "grid_x": pl.grid_x, "grid_y": pl.grid_y, "sweeps": pl.sweeps}
+
+
+def _per_point(t, like, name):
+    """an optional [B,N,3] companion of the cloud ``like`` -> fp32 contiguous on its device"""
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(like.shape):
+        raise ValueError(f"{name} is a tensor of the cloud's shape {list(like.shape)}")
+    if t.device != like.device:
+        raise RuntimeError(f"{name} must be on the cloud's device {like.device} (no CPU fallback)")
+    return t.detach().to(torch.float32).contiguous()
+
+
+def _pca_frames(p, dev_lengths, K, viewpoint=None, want_frame=True):
+    """self-kNN and ``ga_pc_normals`` on an fp32 contiguous cloud [B,N,3] -> (normal, tangent, eigenvalues, dist2, idx); tangent and
+    eigenvalues None unless ``want_frame``.  Two launches on the current stream, no host read."""
+    B, N, _ = p.shape
+    dist2, idx = _knn_forward(p, p, dev_lengths, dev_lengths, K)
+    normal = torch.empty(B, N, 3, dtype=torch.float32, device=p.device)
+    tangent = torch.empty_like(normal) if want_frame else None
+    eig = torch.empty_like(normal) if want_frame else None
+    args = _lib.GaNormalsArgs(B, N, K, 0, p.data_ptr(), _ptr(dev_lengths), idx.data_ptr(), _ptr(viewpoint), normal.data_ptr(),
+                              _ptr(tangent), _ptr(eig))
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().ga_pc_normals(ctypes.byref(args), _stream(p.device)), "ga_pc_normals")
+    return normal, tangent, eig, dist2, idx
+
+
+def _check_k(K, lo, what):
+    K = int(K)
+    if K < lo or K > _lib.GA_PC_KNN_MAX_K:
+        raise ValueError(f"K must lie in [{lo}, {_lib.GA_PC_KNN_MAX_K}] for {what}")
+    return K
+
+
+@torch.no_grad()
+def estimate_normals(points: torch.Tensor, lengths=None, K: int = 16, viewpoint=None, return_frame: bool = False):
+    """PCA normals of a padded batch of clouds [B,N,3] -> ``normals`` [B,N,3] float32, or ``(normals, tangents, eigenvalues)`` with
+    ``return_frame``: per point the covariance of its ``K`` nearest points (itself included; ``knn_points`` of the cloud against
+    itself), the unit eigenvector of the smallest eigenvalue as the normal, that of the largest as the tangent, the eigenvalues
+    ascending.  Sign: the component of largest magnitude is positive; with ``viewpoint`` ([3] or [B,3]) the normal is turned towards
+    it.  Rows past ``lengths``, clouds of fewer than 3 points and points whose neighbours all coincide get normal (0,0,1), tangent
+    (1,0,0), eigenvalues 0.  The definition is the project's own (include/ga_pointcloud.h); normals are not propagated along the
+    surface, so without a viewpoint two neighbours may point to opposite sides.  Two launches on the current stream, no host read."""
+    K = _check_k(K, _lib.GA_PC_NORMALS_MIN_K, "a normal: a plane needs three points")
+    p = _cloud(points, "points")
+    B, N, _ = p.shape
+    dev_lengths, _ = _lengths(lengths, B, N, p.device, "lengths")
+    vp = None
+    if viewpoint is not None:
+        vp = torch.as_tensor(viewpoint, dtype=torch.float32, device=p.device)
+        if tuple(vp.shape) not in ((3,), (B, 3)):
+            raise ValueError(f"viewpoint is [3] or [{B}, 3], not {list(vp.shape)}")
+        vp = vp.expand(B, 3).contiguous()
+    normal, tangent, eig, _, _ = _pca_frames(p, dev_lengths, K, vp, return_frame)
+    return (normal, tangent, eig) if return_frame else normal
+
+
+@torch.no_grad()
+def surfels_from_cloud(points: torch.Tensor, lengths=None, colors=None, normals=None, K: int = 16, opacity: float = 0.1,
+                       scale_factor: float = 1.0):
+    """Activated surfels [B,N,13] (xyz, opacity, scale(2), rotation wxyz, rgb) from a padded batch of clouds: ``ga_pc_surfel_init`` on
+    the PCA frames of ``estimate_normals``.  Scale: ``scale_factor`` times the root mean squared distance to the three nearest other
+    points (2DGS's rule), in both columns; rotation: the disc lies in the tangent plane, its normal the PCA normal or, with
+    ``normals`` [B,N,3], the given one (the PCA tangent is projected onto its plane).  Invalid rows (those of ``estimate_normals``,
+    clouds of fewer than 4 points, a given normal of length 0) get opacity 0, scale 1e-4, the identity rotation."""
+    K = _check_k(K, _lib.GA_PC_SURFEL_MIN_K, "an initial scale: the three nearest other points")
+    if not (0.0 <= float(opacity) <= 1.0) or not (0.0 < float(scale_factor) < float("inf")):
+        raise ValueError("opacity must lie in [0, 1] and scale_factor must be positive and finite")
+    p = _cloud(points, "points")
+    B, N, _ = p.shape
+    dev_lengths, _ = _lengths(lengths, B, N, p.device, "lengths")
+    col = _per_point(colors, p, "colors") if colors is not None else None
+    given = _per_point(normals, p, "normals") if normals is not None else None
+    normal, tangent, eig, dist2, _ = _pca_frames(p, dev_lengths, K)
+    out = torch.empty(B, N, _lib.GA_PC_SURFEL_FLOATS, dtype=torch.float32, device=p.device)
+    args = _lib.GaSurfelInitArgs(B, N, K, float(opacity), float(scale_factor), 0, p.data_ptr(),
+                                 (given if given is not None else normal).data_ptr(), tangent.data_ptr(), dist2.data_ptr(),
+                                 _ptr(dev_lengths), eig.data_ptr(), _ptr(col), out.data_ptr())
+    with torch.cuda.device(p.device):
+        _lib.check(_lib.lib().ga_pc_surfel_init(ctypes.byref(args), _stream(p.device)), "ga_pc_surfel_init")
+    return out

@@ -1,6 +1,8 @@
 /*
  * ga_pointcloud.h -- C-ABI of the MI355X-native point-cloud operations on the generation side: farthest point sampling,
- * nearest point (the building block of the Chamfer distance), the k nearest neighbours and the gradient of their squared distances.
+ * nearest point (the building block of the Chamfer distance), the k nearest neighbours and the gradient of their squared distances;
+ * and, on the neighbour lists, PCA normals and the initial 2D surfels of a fit (ga_pc_normals, ga_pc_surfel_init: the project's own
+ * definitions, at the end of this file).
  *
  * Replaces, for a cloud the USER hands to stage 2 and for the evaluation hand-off of generated surfels,
  *     pytorch3d.ops.sample_farthest_points      (fps-xyz of the stage-2 entry, /root/reference/nsr/lsgm/flow_matching_trainer.py:1079, :1110-1134;
@@ -149,6 +151,100 @@ typedef struct GaKnnBackwardArgs {
 } GaKnnBackwardArgs;
 
 int ga_pc_knn_backward(const GaKnnBackwardArgs *args, void *stream);
+
+/* ---- normals and the surfel initialiser (csrc/pc_normals.hip) ------------------------------------------------------------------------
+ * The definitions below are the project's own: neither Open3D nor pytorch3d runs here, and the sign rule, the invalid-row rule and
+ * the frame are pinned to no other library.  The arithmetic contract above holds: fp32, every operation rounded
+ * on its own, only + - * / sqrt and comparisons, so tests/_normals_ref.py reproduces every output bit for bit. */
+
+/* Jacobi sweeps of ga_pc_normals.  A numpy restatement of the scheme on a Fibonacci sphere, a noisy plane and the faces of a cube
+ * (2048 points each, K = 8 and 16) converged after 4: off-diagonal over diagonal <= 1e-25 and the normals stopped changing; one more. */
+#define GA_PC_NORMALS_SWEEPS 5
+#define GA_PC_NORMALS_MIN_K 3
+#define GA_PC_SURFEL_MIN_K 4
+#define GA_PC_SURFEL_FLOATS 13
+
+/* PCA normals from the neighbour lists ga_pc_knn wrote for the cloud against ITSELF (query = target = points, both lengths = lengths).
+ * The point's own entry is part of the list and is used like any other neighbour.  For point i of cloud b, with n = lengths[b] (clamped
+ * to 0 .. N), m = min(k, n) and j_k' = idx[b,i,k'] clamped to 0 .. n-1:
+ *     centroid     c_a  = (+0 + p[j_0,a] + p[j_1,a] + ...) / m                                  k' ascending, a = x, y, z
+ *     covariance   A_ab = (+0 + d_0a * d_0b + d_1a * d_1b + ...) / m,  d_k'a = p[j_k',a] - c_a    k' ascending, the six terms a <= b
+ *     trace        (A_xx + A_yy) + A_zz
+ *     eigen-decomposition of A by cyclic Jacobi: V = I, then GA_PC_NORMALS_SWEEPS sweeps of the rotations (p,q) = (0,1), (0,2), (1,2),
+ *     no data-dependent exit; a rotation is skipped only when A_pq is exactly 0; otherwise, r the third index,
+ *         theta = (A_qq - A_pp) / (2 * A_pq);   t = 1 / (|theta| + sqrt(theta * theta + 1));   t = theta >= 0 ? t : -t
+ *         c = 1 / sqrt(t * t + 1);   s = t * c;   h = t * A_pq
+ *         A_pp = A_pp - h;  A_qq = A_qq + h;  A_pq = 0;   (A_rp, A_rq) = (c * A_rp - s * A_rq,  s * A_rp + c * A_rq)
+ *         (V_kp, V_kq) = (c * V_kp - s * V_kq,  s * V_kp + c * V_kq)   for k = 0, 1, 2
+ *     the eigenvalues (the diagonal) and their columns of V are sorted ascending by compare-and-swap (0,1), (1,2), (0,1), swapping only
+ *     on a strict 'greater': the lower index stays first among equals
+ *     normal  = column 0, tangent = column 2, each v / sqrt((vx * vx + vy * vy) + vz * vz), then negated when its component of largest
+ *               magnitude (the first among equal magnitudes) is negative
+ *     with viewpoint: d = viewpoint[b] - p[i]; the normal is negated when ((dx * nx + dy * ny) + dz * nz) < 0 (a dot product of exactly
+ *               0 keeps the default sign)
+ * INVALID rows -- i >= n, m < 3, or a trace of exactly 0 (all neighbours coincide) -- get normal (0,0,1), tangent (1,0,0) and
+ * eigenvalues 0.  Validity never comes from an index value.  One lane per point, no LDS, no atomics, no workspace. */
+typedef struct GaNormalsArgs {
+    int32_t batch;            /* B, 1 .. GA_PC_MAX_BATCH                                                   */
+    int32_t num_points;       /* N, N * 3 < 2^31 and (int64) N * k < 2^31 (the limits of GaKnnArgs)        */
+    int32_t k;                /* GA_PC_NORMALS_MIN_K .. GA_PC_KNN_MAX_K: the row length of idx             */
+    int32_t reserved;         /* 0                                                                         */
+    const float *points;      /* [B,N,3]                                                                   */
+    const int32_t *lengths;   /* [B] or NULL (= all N), clamped by the kernel                              */
+    const int32_t *idx;       /* [B,N,k] as ga_pc_knn wrote it                                             */
+    const float *viewpoint;   /* [B,3] or NULL                                                             */
+    float *normal;            /* [B,N,3]                                                                   */
+    float *tangent;           /* [B,N,3] or NULL: the unit eigenvector of the largest eigenvalue           */
+    float *eigenvalues;       /* [B,N,3] or NULL: ascending                                                */
+} GaNormalsArgs;
+
+/* what ga_pc_normals and ga_pc_surfel_init launch: grid (grid_x, grid_y * B) workgroups of `threads` lanes, one lane per point */
+typedef struct GaNormalsPlan {
+    int32_t threads; /* points per workgroup   */
+    int32_t grid_x;  /* ceil(N / threads)      */
+    int32_t grid_y;  /* 1                      */
+    int32_t sweeps;  /* GA_PC_NORMALS_SWEEPS   */
+} GaNormalsPlan;
+
+/* host only, no HIP call: GA_OK, GA_ERR_NULL_ARG or GA_ERR_BAD_SHAPE (k < 3, k > GA_PC_KNN_MAX_K, the limits of GaKnnArgs) */
+int ga_pc_normals_plan(int32_t num_points, int32_t k, GaNormalsPlan *plan);
+int ga_pc_normals(const GaNormalsArgs *args, void *stream);
+
+/* Activated surfels [B,N,13] -- xyz, opacity, scale(2), rotation wxyz, rgb, the layout fitting.to_raw takes -- from a cloud, a normal
+ * and a tangent per point and the squared distances of the same self-kNN call (k >= 4).  For a valid point:
+ *     scale     s = scale_factor * sqrt(max(((d2[1] + d2[2]) + d2[3]) / 3, 1e-7)) in both columns: 2DGS's distCUDA2 rule over the three
+ *               nearest OTHER points (slot 0 is the point itself)
+ *     frame     n = n / sqrt((nx * nx + ny * ny) + nz * nz);   d = (tx * nx + ty * ny) + tz * nz;   u = t - d * n;
+ *               t' = u / sqrt((ux * ux + uy * uy) + uz * uz);   b = n x t' = (ny * t'z - nz * t'y, nz * t'x - nx * t'z, nx * t'y - ny * t'x)
+ *               R = the matrix with the columns (t', b, n)
+ *     rotation  Shepperd's branches in this order, tr = (R00 + R11) + R22:
+ *                 tr > 0:                 S = sqrt(tr + 1) * 2;                  q = (S / 4, (R21 - R12) / S, (R02 - R20) / S, (R10 - R01) / S)
+ *                 R00 > R11 && R00 > R22: S = sqrt(((1 + R00) - R11) - R22) * 2; q = ((R21 - R12) / S, S / 4, (R01 + R10) / S, (R02 + R20) / S)
+ *                 R11 > R22:              S = sqrt(((1 + R11) - R00) - R22) * 2; q = ((R02 - R20) / S, (R01 + R10) / S, S / 4, (R12 + R21) / S)
+ *                 otherwise:              S = sqrt(((1 + R22) - R00) - R11) * 2; q = ((R10 - R01) / S, (R02 + R20) / S, (R12 + R21) / S, S / 4)
+ *               (S / 4 is 0.25 * S), then q / sqrt(((w * w + x * x) + y * y) + z * z), then negated when w < 0
+ *     opacity, and rgb = colors[b,i] or 0.5
+ * INVALID rows -- i >= lengths[b], min(k, lengths[b]) < 4, eigenvalues given and not eigenvalues[b,i,2] > 0 (ga_pc_normals writes exactly
+ * 0 on its invalid rows), or a normal or projected tangent of length exactly 0 (or NaN) -- get xyz as given, opacity 0, scale 1e-4, the identity
+ * quaternion and rgb 0.5: such a row renders nothing and densification can prune it. */
+typedef struct GaSurfelInitArgs {
+    int32_t batch;            /* B, 1 .. GA_PC_MAX_BATCH                                                   */
+    int32_t num_points;       /* N, the limits of GaNormalsArgs                                            */
+    int32_t k;                /* GA_PC_SURFEL_MIN_K .. GA_PC_KNN_MAX_K: the row length of dist2            */
+    float opacity;
+    float scale_factor;
+    int32_t reserved;         /* 0                                                                         */
+    const float *points;      /* [B,N,3]                                                                   */
+    const float *normal;      /* [B,N,3]: ga_pc_normals's, or the caller's (any positive length)           */
+    const float *tangent;     /* [B,N,3]                                                                   */
+    const float *dist2;       /* [B,N,k] as ga_pc_knn wrote it for the cloud against itself                */
+    const int32_t *lengths;   /* [B] or NULL (= all N), clamped by the kernel                              */
+    const float *eigenvalues; /* [B,N,3] or NULL                                                           */
+    const float *colors;      /* [B,N,3] or NULL (= 0.5)                                                   */
+    float *gaussians;         /* [B,N,13]                                                                  */
+} GaSurfelInitArgs;
+
+int ga_pc_surfel_init(const GaSurfelInitArgs *args, void *stream);
 
 #ifdef __cplusplus
 }
