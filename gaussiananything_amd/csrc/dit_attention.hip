@@ -26,13 +26,16 @@
 //   * a caller that wants K normalised here (k_norm_weight != NULL) gets the register-staged variant: K rows are
 //     RMS-normalised by the 8 lanes that stage a row (3 xor-shuffles); Q rows by the 4 lane-groups that hold a row's
 //     fragments; the softmax scale and log2(e) are folded into Q so the exponentials are bare v_exp_f32.
+// The parts this kernel has in common with attention_short_kernel (dit_attention_short.hip) live in dit_attention_common.h: the tile
+// constants and the swizzle, the DMA instruction, the lane-group maximum, the K fragment reads and MFMAs of S^T, the Q fragments read
+// from memory, the ring-independent pieces of the q projection inside the workgroup, and the argument checks of the plans.
 #include <stdlib.h>
 
 #include <algorithm>
 
 #include <type_traits>
 
-#include "dit_common.h"
+#include "dit_attention_common.h"
 
 namespace gadit {
 
@@ -48,8 +51,6 @@ __device__ unsigned long long g_attn_stamps[8 * 16 * 16];
 #define STAMP(k) do { } while (0)
 #endif
 
-constexpr int KB = 64, HD = 64;
-constexpr int TILE = KB * HD;  // elements of one staged tile (8 KiB)
 #ifndef GA_ATTN_HEAD_MAJOR
 #define GA_ATTN_HEAD_MAJOR 1
 #endif
@@ -57,27 +58,6 @@ constexpr int TILE = KB * HD;  // elements of one staged tile (8 KiB)
 #define GA_ATTN_ABLATE 0   // tools/attn_ablate.sh builds timing-only variants with phases removed (wrong results)
 #endif
 constexpr float kLazy = 8.f;    // log2 units a row maximum may exceed its reference before the reference moves
-
-__device__ __forceinline__ int swz_of(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ swz_of(row)) * 8); }
-
-__device__ __forceinline__ void glds16(const uint16_t *gsrc, uint16_t *lds_wave_base)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-
-// max over the four lane groups that hold one query's keys (lanes l, l^16, l^32, l^48): two VALU lane swaps instead of two
-// LDS round trips (ds_bpermute) on the tile's critical path
-__device__ __forceinline__ float group_max(float t)
-{
-    const unsigned u = __float_as_uint(t);
-    const auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const float m = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    const unsigned v = __float_as_uint(m);
-    const auto c = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    return fmaxf(__uint_as_float(c[0]), __uint_as_float(c[1]));
-}
 
 // NW query waves x KS key groups per workgroup.  Wave (ks, wq) owns query rows wq*16 .. +15 of the workgroup's NW*16 and
 // the 64-key tiles ks, ks + KS, ks + 2 KS, ...; every key group stages its own K / V^T tiles (KS rings in LDS) and the
@@ -176,76 +156,21 @@ __global__ __launch_bounds__(NW * KS * 64) void attention_fwd_kernel(GaAttention
     // ---- Q fragments (B operand of S^T = K Q^T): lane holds Q[q0 + c16][kk*32 + g*8 .. +7], normalised, scaled
     bf16x8 qf[2];
     if (!KNORM && NW == 4 && TPS == 1 && a.qp_a != nullptr) {   // kernel-uniform
-        // THE Q PROJECTION INSIDE THE WORKGROUP (round 5; GaAttentionArgs.qp_*): Q[64 queries x 64] of this head = A rows x W_head^T over
-        // K = qp_k, instead of a GEMM launch of its own in front of the attention (the cross-attention of the denoiser: one launch and
-        // the q round trip through memory less per block).  A 64-wide K-slice of W_head is 64 rows x 128 bytes -- the shape of a K tile
-        // -- and so is the slice of the workgroup's 64 A rows: both are staged by the key walk's LDS-DMA pattern, W into the K ring of
-        // the wave's key group (read with the K walk's permuted fragment rows), A into its V^T ring (read with the V^T walk's natural
-        // rows), which leaves the accumulators of S^T = W_slice A_slice^T in exactly the lanes the Q fragments live in:
-        // acc[kf][r] <-> Q[q0 + c16][32 (kf >> 1) + 8 g + 4 (kf & 1) + r].  The key groups split the K-slices (group ks takes slices
-        // ks, ks + KS, ...) and their partial sums meet in LDS in a fixed order.  Ring: 3 slots, two slices ahead; one counted vmcnt
-        // + one raw barrier per slice as in the key walk (everything is DMA: no compiler-managed load sits in the pipeline -- with the
-        // A fragments as register loads hipcc put s_waitcnt vmcnt(0) in front of every DMA issue of the loop).  The request stream
-        // simply continues into the key walk: request group G is W / A slice group G while G < steps_q and stage G - steps_q of the key
-        // walk after that (both are four DMA instructions per wave), so the walk's first two K / V^T stages are already in flight
-        // when the projection ends and it starts with the slots rotated to where they landed.
+        // THE Q PROJECTION INSIDE THE WORKGROUP (round 5; QProjection, dit_attention_common.h: the cross-attention of the denoiser, one
+        // launch and the q round trip through memory less per block).  Here the W slices go into the K ring of the wave's key group and
+        // the A slices into its V^T ring.  The key groups split the K-slices (group ks takes slices ks, ks + KS, ...) and their partial
+        // sums meet in LDS in a fixed order.  Ring: 3 slots, two slices ahead; one counted vmcnt + one raw barrier per slice as in the
+        // key walk.  The request stream simply continues into the key walk: request group G is W / A slice group G while G < steps_q
+        // and stage G - steps_q of the key walk after that (both are four DMA instructions per wave), so the walk's first two K / V^T
+        // stages are already in flight when the projection ends and it starts with the slots rotated to where they landed.
         constexpr int DPQ = 4;                      // DMA instructions per wave per slice: two W pieces + two A pieces of 8 rows
-        const int nsl = a.qp_k >> 6, steps_q = (nsl + KS - 1) / KS;
-        const int qbase = q0 - wq * 16;             // first query row of the workgroup
-        float tot = 0.f;
-        if (a.qp_row_ss) {   // RMSNorm row scale folded out of the A operand (same summation order as the GEMM consumer); used after the loop
-            const float *rp = a.qp_row_ss + ((size_t)b * Lq + min(q0 + c16, Lq - 1)) * a.qp_row_ss_tiles;
-            for (int t4 = 0; t4 < a.qp_row_ss_tiles; t4 += 4) {
-                const float4 q4 = *reinterpret_cast<const float4 *>(rp + t4);
-                tot += (q4.x + q4.y) + (q4.z + q4.w);
-            }
-        }
+        QProjection qp;
+        qp.setup(a, b, h, q0, wq, lane);
+        const int steps_q = (qp.nsl + KS - 1) / KS;
         static_assert(KNORM || TPS != 1 || NW != 4 || DPW * TPS == 4, "a stage of the key walk is four DMA instructions per wave, like a slice group");
-        float qnw[16];       // per-head norm weights of my 16 head columns, requested in front of the DMA stream (a load behind it would wait for all of it)
-        {
-            float4 w4[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) w4[i] = make_float4(1.f, 1.f, 1.f, 1.f);
-            if (a.q_norm_weight) {   // kernel-uniform
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    w4[2 * kk] = *reinterpret_cast<const float4 *>(a.q_norm_weight + kk * 32 + g * 8);
-                    w4[2 * kk + 1] = *reinterpret_cast<const float4 *>(a.q_norm_weight + kk * 32 + g * 8 + 4);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { qnw[4 * i] = w4[i].x; qnw[4 * i + 1] = w4[i].y; qnw[4 * i + 2] = w4[i].z; qnw[4 * i + 3] = w4[i].w; }
-        }
-        // (round 6: as in the key walk, a lane's byte offsets once, a slice's address = wave-uniform base + offset)
-        uint32_t qw_off[2], qa_off[2];
-        const char *qw_base[2];
-        const char *qa_base = reinterpret_cast<const char *>(a.qp_a + (size_t)b * Lq * a.qp_lda);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int p = wq * 2 + i, r8 = p * 8, row = r8 + (lane >> 3), chunk = (lane & 7) ^ swz_of(row);
-            if (a.qp_w_tiled) {    // kernel-uniform
-                qw_base[i] = reinterpret_cast<const char *>(a.qp_w + (size_t)(h * 8 + p) * nsl * 512);
-                qw_off[i] = (uint32_t)((lane >> 3) * 64 + chunk * 8) * 2u;
-            } else {
-                qw_base[i] = reinterpret_cast<const char *>(a.qp_w + (size_t)h * 64 * a.qp_k);
-                qw_off[i] = ((uint32_t)row * (uint32_t)a.qp_k + (uint32_t)chunk * 8u) * 2u;
-            }
-            qa_off[i] = ((uint32_t)min(qbase + row, Lq - 1) * (uint32_t)a.qp_lda + (uint32_t)chunk * 8u) * 2u;
-        }
-        const uint32_t qw_step = a.qp_w_tiled ? 1024u : 128u;     // bytes from one 64-wide K-slice of W to the next
         auto dma_q = [&](int grp, int slot) {
             if (grp >= steps_q) { dma_stage((grp - steps_q) * KS + ks, slot); return; }   // the key walk's stages 0, 1 (workgroup-uniform)
-            const int sl = min(grp * KS + ks, nsl - 1);   // past the end: a harmless re-fetch (keeps the vmcnt arithmetic exact)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int r8 = (wq * 2 + i) * 8;
-                glds16(reinterpret_cast<const uint16_t *>(qw_base[i] + (size_t)sl * qw_step + qw_off[i]), sK + slot * TILE + r8 * 64);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int r8 = (wq * 2 + i) * 8;
-                glds16(reinterpret_cast<const uint16_t *>(qa_base + (size_t)sl * 128 + qa_off[i]), sV + slot * TILE + r8 * 64);
-            }
+            qp.issue(grp * KS + ks, sK + slot * TILE, sV + slot * TILE);
         };
         f32x4 acc[4];
 #pragma unroll
@@ -257,7 +182,7 @@ __global__ __launch_bounds__(NW * KS * 64) void attention_fwd_kernel(GaAttention
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(DPQ) : "memory");   // my pieces of slice group t; group t + 1 may be in flight
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
-            if (t * KS + ks < nsl) {   // group-uniform
+            if (t * KS + ks < qp.nsl) {   // group-uniform.  (The slice step, as in attention_short_kernel: not a shared helper, see dit_attention_common.h)
                 const uint16_t *bk = sK + s0 * TILE, *bx = sV + s0 * TILE;
                 bf16x8 frag[4][2], xf[2];
 #pragma unroll
@@ -302,61 +227,9 @@ __global__ __launch_bounds__(NW * KS * 64) void attention_fwd_kernel(GaAttention
                 }
             // (slot s2 is overwritten by the key walk's stage 2, requested behind the barrier of its first step: everybody has read by then)
         }
-        const float rsc = a.qp_row_ss ? rsqrtf(tot * (1.0f / (float)a.qp_row_ss_dim) + a.qp_row_ss_eps) : 1.f;
-        // row scale, per-head RMSNorm, bf16 as the projection GEMM would have stored it, then the softmax scale as below
-        float xv[16];
-        float ss = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float v = acc[2 * kk + (e >> 2)][e & 3] * rsc;
-                xv[kk * 8 + e] = v;
-                ss += v * v;
-            }
-        ss += __shfl_xor(ss, 16, 64);
-        ss += __shfl_xor(ss, 32, 64);
-        const float rn = rsqrtf(ss * (1.0f / HD) + 1e-5f);
-        const float rs = 0.125f * 1.4426950408889634f;  // 64^-1/2 * log2(e)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float v = xv[kk * 8 + e];
-                if (a.q_norm_weight) v *= rn * qnw[kk * 8 + e];
-                qf[kk][e] = (short)f32_to_bf16(bf16_to_f32(f32_to_bf16(v)) * rs);
-            }
+        qp.finish(a, acc, qf);
     } else {
-        {
-            const int row = min(q0 + c16, Lq - 1);
-            const uint16_t *qp = a.q + ((size_t)b * Lq + row) * a.q_stride + h * HD;
-            float qv[16];
-            float ss = 0.f;
-    #pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const uint4 raw = *reinterpret_cast<const uint4 *>(qp + kk * 32 + g * 8);
-                const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
-    #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    qv[kk * 8 + 2 * e] = __uint_as_float(w[e] << 16);
-                    qv[kk * 8 + 2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
-                }
-            }
-    #pragma unroll
-            for (int e = 0; e < 16; ++e) ss += qv[e] * qv[e];
-            ss += __shfl_xor(ss, 16, 64);
-            ss += __shfl_xor(ss, 32, 64);
-            float rs = 0.125f * 1.4426950408889634f;  // 64^-1/2 * log2(e)
-            if (a.q_norm_weight) rs *= rsqrtf(ss * (1.0f / HD) + 1e-5f);
-    #pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-    #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    float v = qv[kk * 8 + e];
-                    if (a.q_norm_weight) v *= a.q_norm_weight[kk * 32 + g * 8 + e];
-                    qf[kk][e] = (short)f32_to_bf16(v * rs);
-                }
-        }
+        q_frags_from_memory(a, b, h, min(q0 + c16, Lq - 1), g, qf);
     }
 
     f32x4 o[4];
@@ -418,12 +291,7 @@ __global__ __launch_bounds__(NW * KS * 64) void attention_fwd_kernel(GaAttention
         // through one register quad: read -> wait -> MFMA, eight LDS latencies in a row, twice per tile); the V^T
         // fragments are requested as soon as the S MFMAs have consumed the K fragments and land while the softmax runs.
         bf16x8 frag[4][2];
-        const int krow = 8 * (c16 >> 2) + (c16 & 3);
-#pragma unroll
-        for (int kf = 0; kf < 4; ++kf)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-                frag[kf][kk] = *reinterpret_cast<const bf16x8 *>(bk + swz((kf >> 1) * 32 + (kf & 1) * 4 + krow, kk * 4 + g));
+        kq_frags(bk, c16, g, frag);
         __builtin_amdgcn_sched_barrier(0);
         STAMP(2);
 
@@ -432,11 +300,7 @@ __global__ __launch_bounds__(NW * KS * 64) void attention_fwd_kernel(GaAttention
         const float nm = -m_run;
 #pragma unroll
         for (int kf = 0; kf < 4; ++kf) s[kf] = f32x4{nm, nm, nm, nm};
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int kf = 0; kf < 4; ++kf)
-                if (GA_ATTN_ABLATE != 2) s[kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag[kf][kk], qf[kk], s[kf], 0, 0, 0);
+        if (GA_ATTN_ABLATE != 2) kq_mfma(frag, qf, s);
         __builtin_amdgcn_sched_barrier(0);
         STAMP(3);
         // the next-but-one tile's DMA is requested here, behind the head of the step's dependency chain (K fragments ->
@@ -646,17 +510,9 @@ static void fill_attention_plan(const AttnConfig &c, const GaAttentionArgs *a, G
 static int attention_plan(const GaAttentionArgs *a, GaAttentionPlan *pl)
 {
     if (!a || (!a->q && !a->qp_a) || !a->k || !a->vt || !a->out) return GA_DIT_ERR_NULL_ARG;
-    if (a->qp_a) {   // the q projection inside the workgroup: LDS-DMA path only, 16-byte aligned operands, K in 64-wide slices
-        if (!a->qp_w || a->k_norm_weight) return GA_DIT_ERR_NULL_ARG;
-        if (a->qp_k < 64 || a->qp_k % 64 || a->qp_lda % 8 || a->qp_lda < a->qp_k || ((uintptr_t)a->qp_a | (uintptr_t)a->qp_w) % 16 != 0 ||
-            (a->qp_row_ss && (a->qp_row_ss_tiles <= 0 || a->qp_row_ss_tiles % 4 != 0 || a->qp_row_ss_dim <= 0 || (uintptr_t)a->qp_row_ss % 16 != 0)))
-            return GA_DIT_ERR_BAD_SHAPE;
-    }
-    if (a->batch <= 0 || a->heads <= 0 || a->Lq <= 0 || a->Lk <= 0 || a->q_stride % 8 || a->k_stride % 8 || a->vt_ld % 8 ||
-        a->vt_ld < ((a->Lk + KB - 1) / KB) * KB || a->out_stride % 4)
-        return GA_DIT_ERR_BAD_SHAPE;
-    // 16-byte accesses (vector loads of q, LDS-DMA of k / vt, 8-byte stores of out)
-    if (((a->qp_a ? 0 : (uintptr_t)a->q) | (uintptr_t)a->k | (uintptr_t)a->vt) % 16 != 0 || (uintptr_t)a->out % 8 != 0) return GA_DIT_ERR_BAD_SHAPE;
+    if (a->qp_a && a->k_norm_weight) return GA_DIT_ERR_NULL_ARG;   // the q projection inside the workgroup: LDS-DMA path only
+    const int rc = attention_args_check(a);
+    if (rc != GA_DIT_OK) return rc;
     const AttnConfig c = attention_config(a);
     if (a->qp_a && (c.tuned || c.nw != 4 || c.ks != 3)) return GA_DIT_ERR_BAD_SHAPE;   // only the 64-query configuration projects q itself (attention_fuses_q)
     fill_attention_plan(c, a, pl);

@@ -15,19 +15,9 @@
 
 #include <type_traits>
 
-#include "dit_common.h"
+#include "dit_attention_common.h"   // group_max (the lane-group maximum of the head-64 kernels)
 
 namespace gadit {
-
-__device__ __forceinline__ float group_max_hd(float t)   // over lanes l, l^16, l^32, l^48 (the four lane groups of one query)
-{
-    const unsigned u = __float_as_uint(t);
-    const auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const float m = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    const unsigned v = __float_as_uint(m);
-    const auto c = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    return fmaxf(__uint_as_float(c[0]), __uint_as_float(c[1]));
-}
 
 // HDP: head dim rounded up to a multiple of 32.  Workgroup = 4 waves x 16 queries; grid (ceil(Lq / 64), heads, batch).
 template <int HDP>
@@ -105,7 +95,7 @@ __global__ __launch_bounds__(256) void attention_hd_kernel(GaAttentionHdArgs a)
                 if (kbase + (kf >> 1) * 32 + (kf & 1) * 4 + r >= Lk) s[kf][r] = -1e30f;
                 tmax = fmaxf(tmax, s[kf][r]);
             }
-        tmax = group_max_hd(tmax);
+        tmax = group_max(tmax);
         const float m_new = fmaxf(m_run, tmax);
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
         m_run = m_new;
@@ -400,7 +390,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 2)))
                     if (edge && kbase + (kf >> 1) * 32 + (kf & 1) * 4 + r >= Lk) s[f][kf][r] = -1e30f;
                     tmax = fmaxf(tmax, s[f][kf][r]);
                 }
-            tmax = group_max_hd(tmax);
+            tmax = group_max(tmax);
             const float m_new = fmaxf(m_run[f], tmax * cs);
             const float alpha = __builtin_amdgcn_exp2f(m_run[f] - m_new);
             m_run[f] = m_new;

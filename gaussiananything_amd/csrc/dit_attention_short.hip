@@ -6,45 +6,27 @@
 // does:
 //   * a workgroup = 4 waves x 16 queries of one (batch, head); grid (heads * batch, ceil(Lq / 64)) head-major as in dit_attention.hip;
 //   * K and V^T of the head (at most two 64-key tiles each, 32 KiB) are staged ONCE by LDS-DMA, requested before anything else, in the
-//     swizzled row-major image of dit_attention.hip (same fragment reads, same lane <-> element maps);
+//     swizzled row-major image of dit_attention.hip (the fragment reads and lane <-> element maps are the same code:
+//     dit_attention_common.h);
 //   * one S^T = K Q^T pass over at most 8 key fragments (key columns >= Lk masked), ONE-PASS softmax with the true row maximum -- no
 //     rescale, no merge --, then O^T = V^T P^T;
-//   * q is either given or projected inside the workgroup (GaAttentionArgs.qp_*) with the semantics of attention_fwd_kernel<4,3>'s
-//     projection: A / W K-slices staged by LDS-DMA into a three-slot ring of their own (two slices ahead, one counted vmcnt + one raw
-//     barrier per slice), fp32 accumulation over the slices in order, row scale, per-head RMSNorm, rounded to bf16 as the projection
-//     GEMM would have stored it, then the softmax scale.
+//   * q is either given or projected inside the workgroup (GaAttentionArgs.qp_*) by the code attention_fwd_kernel<4,3> projects it
+//     with (QProjection, dit_attention_common.h: fp32 accumulation over the slices in order, row scale, per-head RMSNorm, rounded to
+//     bf16 as the projection GEMM would have stored it, then the softmax scale); this kernel's own part is how the slices arrive: A /
+//     W K-slices staged by LDS-DMA into a three-slot ring behind the K / V^T tiles (two slices ahead, one counted vmcnt + one raw
+//     barrier per slice), every wave taking every slice.
 // vmcnt accounting: every wave issues its K / V^T DMA instructions first (4 per key tile: 4 or 8), then 4 per K-slice of the projection;
 // waiting for slice t with slice t + 1 in flight is vmcnt(4) -- the counter retires in order, so everything older than the 4
 // instructions of slice t + 1, the K / V^T pieces included, has landed by the first such wait.
 // LDS: the K / V^T tiles of the instantiation (16 KiB per key tile) and, only where q is projected inside (QP), the 48 KiB ring.
 #include <algorithm>
 
-#include "dit_common.h"
+#include "dit_attention_common.h"
 
 namespace gadit {
 namespace {
 
-constexpr int KB = 64, HD = 64, TILE = KB * HD, SQ = 64, MAXT = 2;
-
-__device__ __forceinline__ int swz_of(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }
-__device__ __forceinline__ int swz(int row, int chunk) { return row * 64 + ((chunk ^ swz_of(row)) * 8); }
-
-__device__ __forceinline__ void glds16(const uint16_t *gsrc, uint16_t *lds_wave_base)
-{
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)gsrc,
-                                     (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-
-// max over the four lane groups that hold one query's keys (lanes l, l^16, l^32, l^48)
-__device__ __forceinline__ float group_max(float t)
-{
-    const unsigned u = __float_as_uint(t);
-    const auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const float m = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    const unsigned v = __float_as_uint(m);
-    const auto c = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    return fmaxf(__uint_as_float(c[0]), __uint_as_float(c[1]));
-}
+constexpr int SQ = 64, MAXT = 2;
 
 // workgroups behind the attention grid (y slices >= y0) that pull weight ranges towards the Infinity Cache (dit_common.h: PrefetchJob) on
 // the CUs the grid leaves idle; nwgs == 0: none
@@ -89,55 +71,12 @@ __global__ __launch_bounds__(256) void attention_short_kernel(GaAttentionArgs a,
 
     // ---- Q fragments (B operand of S^T = K Q^T): lane holds Q[q0 + c16][kk*32 + g*8 .. +7], normalised, scaled
     bf16x8 qf[2];
-    if constexpr (QP) {   // the q projection inside the workgroup
-        const int nsl = a.qp_k >> 6;
-        const int qbase = q0 - wq * 16;
-        float tot = 0.f;
-        if (a.qp_row_ss) {   // RMSNorm row scale folded out of the A operand (same summation order as the GEMM consumer)
-            const float *rp = a.qp_row_ss + ((size_t)b * Lq + min(q0 + c16, Lq - 1)) * a.qp_row_ss_tiles;
-            for (int t4 = 0; t4 < a.qp_row_ss_tiles; t4 += 4) {
-                const float4 q4 = *reinterpret_cast<const float4 *>(rp + t4);
-                tot += (q4.x + q4.y) + (q4.z + q4.w);
-            }
-        }
-        float qnw[16];
-        {
-            float4 w4[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) w4[i] = make_float4(1.f, 1.f, 1.f, 1.f);
-            if (a.q_norm_weight) {   // kernel-uniform
-#pragma unroll
-                for (int kk = 0; kk < 2; ++kk) {
-                    w4[2 * kk] = *reinterpret_cast<const float4 *>(a.q_norm_weight + kk * 32 + g * 8);
-                    w4[2 * kk + 1] = *reinterpret_cast<const float4 *>(a.q_norm_weight + kk * 32 + g * 8 + 4);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { qnw[4 * i] = w4[i].x; qnw[4 * i + 1] = w4[i].y; qnw[4 * i + 2] = w4[i].z; qnw[4 * i + 3] = w4[i].w; }
-        }
-        uint32_t qw_off[2], qa_off[2];
-        const char *qw_base[2];
-        const char *qa_base = reinterpret_cast<const char *>(a.qp_a + (size_t)b * Lq * a.qp_lda);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int p = wq * 2 + i, r8 = p * 8, row = r8 + (lane >> 3), chunk = (lane & 7) ^ swz_of(row);
-            if (a.qp_w_tiled) {    // kernel-uniform
-                qw_base[i] = reinterpret_cast<const char *>(a.qp_w + (size_t)(h * 8 + p) * nsl * 512);
-                qw_off[i] = (uint32_t)((lane >> 3) * 64 + chunk * 8) * 2u;
-            } else {
-                qw_base[i] = reinterpret_cast<const char *>(a.qp_w + (size_t)h * 64 * a.qp_k);
-                qw_off[i] = ((uint32_t)row * (uint32_t)a.qp_k + (uint32_t)chunk * 8u) * 2u;
-            }
-            qa_off[i] = ((uint32_t)min(qbase + row, Lq - 1) * (uint32_t)a.qp_lda + (uint32_t)chunk * 8u) * 2u;
-        }
-        const uint32_t qw_step = a.qp_w_tiled ? 1024u : 128u;     // bytes from one 64-wide K-slice of W to the next
+    if constexpr (QP) {   // the q projection inside the workgroup (QProjection, dit_attention_common.h), slice by slice through a ring of its own
+        QProjection qp;
+        qp.setup(a, b, h, q0, wq, lane);
         auto dma_q = [&](int sl_raw, int slot) {
-            const int sl = min(sl_raw, nsl - 1);   // past the end: a harmless re-fetch (keeps the vmcnt arithmetic exact)
-            uint16_t *dw = sR + slot * 2 * TILE, *da = dw + TILE;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) glds16(reinterpret_cast<const uint16_t *>(qw_base[i] + (size_t)sl * qw_step + qw_off[i]), dw + (wq * 2 + i) * 8 * 64);
-#pragma unroll
-            for (int i = 0; i < 2; ++i) glds16(reinterpret_cast<const uint16_t *>(qa_base + (size_t)sl * 128 + qa_off[i]), da + (wq * 2 + i) * 8 * 64);
+            uint16_t *dw = sR + slot * 2 * TILE;
+            qp.issue(sl_raw, dw, dw + TILE);
         };
         f32x4 acc[4];
 #pragma unroll
@@ -146,12 +85,12 @@ __global__ __launch_bounds__(256) void attention_short_kernel(GaAttentionArgs a,
         int s0 = 0, s1 = 1, s2 = 2;
         dma_q(0, 0);
         dma_q(1, 1);
-        for (int t = 0; t < nsl; ++t) {
+        for (int t = 0; t < qp.nsl; ++t) {
             asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // my pieces of slice t (and of K / V^T, issued before); slice t + 1 may be in flight
             __builtin_amdgcn_s_barrier();                        // everyone's pieces have landed, everyone has left slice t - 1
             __builtin_amdgcn_sched_barrier(0);
             const uint16_t *bk = sR + s0 * 2 * TILE, *bx = bk + TILE;
-            bf16x8 frag[4][2], xf[2];
+            bf16x8 frag[4][2], xf[2];      // (the slice step, as in attention_fwd_kernel's projection: not a shared helper, see dit_attention_common.h)
 #pragma unroll
             for (int kf = 0; kf < 4; ++kf)
 #pragma unroll
@@ -169,82 +108,23 @@ __global__ __launch_bounds__(256) void attention_short_kernel(GaAttentionArgs a,
             __builtin_amdgcn_sched_barrier(0);
             const int r = s0; s0 = s1; s1 = s2; s2 = r;
         }
-        const float rsc = a.qp_row_ss ? rsqrtf(tot * (1.0f / (float)a.qp_row_ss_dim) + a.qp_row_ss_eps) : 1.f;
-        // row scale, per-head RMSNorm, bf16 as the projection GEMM would have stored it, then the softmax scale
-        float xv[16];
-        float ss = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const float v = acc[2 * kk + (e >> 2)][e & 3] * rsc;
-                xv[kk * 8 + e] = v;
-                ss += v * v;
-            }
-        ss += __shfl_xor(ss, 16, 64);
-        ss += __shfl_xor(ss, 32, 64);
-        const float rn = rsqrtf(ss * (1.0f / HD) + 1e-5f);
-        const float rs = 0.125f * 1.4426950408889634f;  // 64^-1/2 * log2(e)
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float v = xv[kk * 8 + e];
-                if (a.q_norm_weight) v *= rn * qnw[kk * 8 + e];
-                qf[kk][e] = (short)f32_to_bf16(bf16_to_f32(f32_to_bf16(v)) * rs);
-            }
+        qp.finish(a, acc, qf);
     } else {
-        const int row = min(q0 + c16, Lq - 1);
-        const uint16_t *qp = a.q + ((size_t)b * Lq + row) * a.q_stride + h * HD;
-        float qv[16];
-        float ss = 0.f;
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-            const uint4 raw = *reinterpret_cast<const uint4 *>(qp + kk * 32 + g * 8);
-            const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                qv[kk * 8 + 2 * e] = __uint_as_float(w[e] << 16);
-                qv[kk * 8 + 2 * e + 1] = __uint_as_float(w[e] & 0xffff0000u);
-            }
-        }
-#pragma unroll
-        for (int e = 0; e < 16; ++e) ss += qv[e] * qv[e];
-        ss += __shfl_xor(ss, 16, 64);
-        ss += __shfl_xor(ss, 32, 64);
-        float rs = 0.125f * 1.4426950408889634f;  // 64^-1/2 * log2(e)
-        if (a.q_norm_weight) rs *= rsqrtf(ss * (1.0f / HD) + 1e-5f);
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float v = qv[kk * 8 + e];
-                if (a.q_norm_weight) v *= a.q_norm_weight[kk * 32 + g * 8 + e];
-                qf[kk][e] = (short)f32_to_bf16(v * rs);
-            }
+        q_frags_from_memory(a, b, h, min(q0 + c16, Lq - 1), g, qf);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // K / V^T (and the projection's last re-fetches: no DMA outlives the workgroup's LDS)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- S^T = K Q^T : s[tile][kf][r] <-> key 64 tile + (kf>>1)*32 + g*8 + (kf&1)*4 + r, query c16
-    const int krow = 8 * (c16 >> 2) + (c16 & 3);
     f32x4 s[NT][4];
 #pragma unroll
     for (int tile = 0; tile < NT; ++tile) {
-        const uint16_t *bk = sK + tile * TILE;
         bf16x8 frag[4][2];
-#pragma unroll
-        for (int kf = 0; kf < 4; ++kf)
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-                frag[kf][kk] = *reinterpret_cast<const bf16x8 *>(bk + swz((kf >> 1) * 32 + (kf & 1) * 4 + krow, kk * 4 + g));
+        kq_frags(sK + tile * TILE, c16, g, frag);
 #pragma unroll
         for (int kf = 0; kf < 4; ++kf) s[tile][kf] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-            for (int kf = 0; kf < 4; ++kf) s[tile][kf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag[kf][kk], qf[kk], s[tile][kf], 0, 0, 0);
+        kq_mfma(frag, qf, s[tile]);
         if (tile >= nfull) {     // kernel-uniform: the ragged tile
             const int kbase = tile * KB + g * 8;
 #pragma unroll
@@ -312,17 +192,9 @@ int short_plan(const GaAttentionArgs *a, GaAttentionShortPlan *pl)
 {
     if (!a || (!a->q && !a->qp_a) || !a->k || !a->vt || !a->out) return GA_DIT_ERR_NULL_ARG;
     if (a->k_norm_weight) return GA_DIT_ERR_BAD_SHAPE;      // K arrives normalised (once per conditioning, in the projection GEMM)
-    if (a->qp_a) {
-        if (!a->qp_w) return GA_DIT_ERR_NULL_ARG;
-        if (a->qp_k < 64 || a->qp_k % 64 || a->qp_lda % 8 || a->qp_lda < a->qp_k || ((uintptr_t)a->qp_a | (uintptr_t)a->qp_w) % 16 != 0 ||
-            (a->qp_row_ss && (a->qp_row_ss_tiles <= 0 || a->qp_row_ss_tiles % 4 != 0 || a->qp_row_ss_dim <= 0 || (uintptr_t)a->qp_row_ss % 16 != 0)))
-            return GA_DIT_ERR_BAD_SHAPE;
-    }
-    if (a->batch <= 0 || a->heads <= 0 || a->Lq <= 0 || a->Lk <= 0 || a->Lk > MAXT * KB || a->q_stride % 8 || a->k_stride % 8 || a->vt_ld % 8 ||
-        a->vt_ld < ((a->Lk + KB - 1) / KB) * KB || a->out_stride % 4)
-        return GA_DIT_ERR_BAD_SHAPE;
-    if (((a->qp_a ? 0 : (uintptr_t)a->q) | (uintptr_t)a->k | (uintptr_t)a->vt) % 16 != 0 || (uintptr_t)a->out % 8 != 0) return GA_DIT_ERR_BAD_SHAPE;
-    if ((int64_t)a->heads * a->batch > INT32_MAX) return GA_DIT_ERR_BAD_SHAPE;
+    const int rc = attention_args_check(a);
+    if (rc != GA_DIT_OK) return rc;
+    if (a->Lk > MAXT * KB || (int64_t)a->heads * a->batch > INT32_MAX) return GA_DIT_ERR_BAD_SHAPE;
     *pl = GaAttentionShortPlan{};
     pl->queries_per_wg = SQ;
     pl->key_tiles = (a->Lk + KB - 1) / KB;
