@@ -146,6 +146,15 @@ class GaSurfelInitArgs(ctypes.Structure):
                 ("gaussians", ctypes.c_void_p)]
 
 
+class GaUnprojectArgs(ctypes.Structure):
+    """include/ga_pointcloud.h: GaUnprojectArgs"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("num_views", "height", "width", "depth_kind", "color_kind", "erode", "drop_zero",
+                                              "pixel_stride", "capacity")] + \
+               [(n, ctypes.c_float) for n in ("depth_min", "depth_max", "mask_threshold", "clip")] + [("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ("depth", "mask", "color", "normal", "cameras", "points", "colors", "normals", "source",
+                                               "count", "view_counts", "workspace")] + [("workspace_bytes", ctypes.c_size_t)]
+
+
 class GaPhotoLossArgs(ctypes.Structure):
     """include/ga_loss.h: GaPhotoLossArgs"""
     _fields_ = [("num_images", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
@@ -249,12 +258,16 @@ GA_PHOTO_LOSS_SAVE = 1
 GA_GEO_LOSS_TARGET, GA_GEO_LOSS_NORMALS = 1, 2
 GA_PC_KNN_MAX_K = 32
 GA_PC_NORMALS_SWEEPS, GA_PC_NORMALS_MIN_K, GA_PC_SURFEL_MIN_K, GA_PC_SURFEL_FLOATS = 5, 3, 4, 13
+GA_PC_DEPTH_Z, GA_PC_DEPTH_RAY, GA_PC_COLOR_F32, GA_PC_COLOR_U8 = 0, 1, 0, 1
+GA_PC_UNPROJECT_THREADS, GA_PC_UNPROJECT_TILE_PIXELS, GA_PC_UNPROJECT_MAX_WIDTH, GA_PC_UNPROJECT_MAX_ERODE = 256, 1024, 4096, 4
+GA_PC_CAMERA_FLOATS = 21
 
 EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspace_layout2", "ga_surfel_forward", "ga_surfel_postprocess",
            "ga_surfel_backward", "ga_surfel_backward_scratch_bytes", "ga_surfel_store_policy",
            "ga_tsdf_integrate", "ga_tsdf_mesh_scratch_bytes", "ga_tsdf_mesh_count", "ga_tsdf_mesh_emit", "ga_mesh_write_obj", "ga_mesh_cluster_labels",
            "ga_pc_fps", "ga_pc_fps_plan", "ga_pc_fps_workspace_bytes", "ga_pc_nearest",
            "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward", "ga_pc_normals", "ga_pc_normals_plan", "ga_pc_surfel_init",
+           "ga_pc_unproject", "ga_pc_unproject_workspace_bytes",
            "ga_photo_loss_plan", "ga_photo_loss_workspace_bytes", "ga_photo_loss_forward", "ga_photo_loss_backward",
            "ga_geo_loss_plan", "ga_geo_loss_workspace_bytes", "ga_geo_loss_forward", "ga_geo_loss_backward",
            "ga_fit_plan", "ga_fit_activate", "ga_fit_pack_grads", "ga_fit_adam", "ga_fit_advance", "ga_fit_select_views",
@@ -336,6 +349,10 @@ def lib():
         L.ga_pc_normals_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GaNormalsPlan)]
         L.ga_pc_surfel_init.restype = ctypes.c_int
         L.ga_pc_surfel_init.argtypes = [ctypes.POINTER(GaSurfelInitArgs), ctypes.c_void_p]
+        L.ga_pc_unproject.restype = ctypes.c_int
+        L.ga_pc_unproject.argtypes = [ctypes.POINTER(GaUnprojectArgs), ctypes.c_void_p]
+        L.ga_pc_unproject_workspace_bytes.restype = ctypes.c_size_t
+        L.ga_pc_unproject_workspace_bytes.argtypes = [ctypes.c_int32] * 3
         L.ga_photo_loss_plan.restype = ctypes.c_int
         L.ga_photo_loss_plan.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(GaPhotoLossPlan)]
         L.ga_photo_loss_workspace_bytes.restype = ctypes.c_size_t

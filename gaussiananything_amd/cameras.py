@@ -96,6 +96,40 @@ def c_to_3dgs_format_device(poses: torch.Tensor, znear=0.01, zfar=100.0):
                 tanfov=float(tan.reshape(-1)[0]))
 
 
+def cameras_from_view(cam_view: torch.Tensor, tanfov) -> torch.Tensor:
+    """What ``render`` takes -> the [V, 21] cameras ``pointcloud.unproject_depth_views`` takes (include/ga_pointcloud.h: rotation
+    camera-to-world row-major, position, fx, fy, cx, cy, sk, four zeros).  ``cam_view`` [V, 4, 4] is the row-vector world-to-view
+    matrix ``w2c.T`` and must be rigid: its upper 3 x 3 block is then the camera-to-world rotation, the camera sits at
+    ``-(R @ cam_view[3, :3])``, and a symmetric pinhole of half-angle tangent ``tanfov`` has ``fx = fy = 1 / (2 * tanfov)``,
+    ``cx = cy = 0.5``, ``sk = 0`` in the reference's normalised units.  Plain fp32 tensor operations on ``cam_view``'s device."""
+    if not isinstance(cam_view, torch.Tensor) or cam_view.dim() != 3 or tuple(cam_view.shape[1:]) != (4, 4) or cam_view.shape[0] < 1:
+        raise ValueError("cam_view is a [V, 4, 4] tensor")
+    if isinstance(tanfov, torch.Tensor) or not (0.0 < float(tanfov) < float("inf")):
+        raise ValueError("tanfov must be a positive finite number")
+    view = cam_view.detach().to(torch.float32)
+    R = view[:, :3, :3]
+    pos = -(R @ view[:, 3, :3, None])[:, :, 0]
+    out = torch.zeros(view.shape[0], 21, dtype=torch.float32, device=view.device)
+    out[:, :9] = R.reshape(-1, 9)
+    out[:, 9:12] = pos
+    out[:, 12:14] = 1.0 / (2.0 * float(tanfov))
+    out[:, 14:16] = 0.5
+    return out
+
+
+def cameras_from_pose25(poses: torch.Tensor) -> torch.Tensor:
+    """The reference's ``c`` [V, 25] (camera-to-world 4 x 4 row-major, then the normalised 3 x 3 intrinsics) -> the same [V, 21] cameras:
+    a re-ordering, no arithmetic."""
+    if not isinstance(poses, torch.Tensor) or poses.dim() != 2 or poses.shape[1] != 25 or poses.shape[0] < 1:
+        raise ValueError("a pose25 tensor is [V, 25]")
+    c = poses.detach().to(torch.float32)
+    out = torch.zeros(c.shape[0], 21, dtype=torch.float32, device=c.device)
+    out[:, :9] = c[:, [0, 1, 2, 4, 5, 6, 8, 9, 10]]
+    out[:, 9:12] = c[:, [3, 7, 11]]
+    out[:, 12:17] = c[:, [16, 20, 18, 21, 17]]      # fx, fy, cx, cy, sk
+    return out
+
+
 def orbit_poses(num_views, radius=1.77, fx=1.3889, elevation_deg=15.0, seed=None):
     """Synthetic look-at-origin orbit in the pose25 format (c2w + normalised K), for inputs that must not depend
     on reference assets.  Camera looks down its +z axis at the origin (the convention of ``eval_pose.pt``)."""

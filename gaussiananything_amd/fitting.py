@@ -71,7 +71,8 @@ def surfels_from_points(points, colors=None, normals=None, K=16, opacity=0.1, sc
     three nearest other points (2DGS's ``create_from_pcd`` rule; 2DGS draws the rotations at random), its opacity ``opacity``, its
     colour ``colors`` [N,3] in [0, 1] or 0.5.  ``pointcloud.surfels_from_cloud`` on a batch of one: the kNN launch and two
     per-point launches, no host read.  A point whose neighbours all coincide with it gets opacity 0 (``pointcloud.estimate_normals``).
-    Not built: anisotropic initial scales, SH colours, orientation propagation, unprojecting RGB-D views to points."""
+    Posed RGB-D views become such a cloud through ``pointcloud.unproject_depth_views`` (``SurfelFitter.from_rgbd``).
+    Not built: anisotropic initial scales, SH colours, orientation propagation."""
     from . import pointcloud
 
     def batched(t, name):
@@ -474,6 +475,50 @@ class SurfelFitter:
         normals, K, opacity, scale_factor)`` and then the constructor with ``fitter_kwargs``."""
         g = surfels_from_points(points, colors=colors, normals=normals, K=K, opacity=opacity, scale_factor=scale_factor)
         return cls(g, cam_view, cam_view_proj, tanfov, targets, **fitter_kwargs)
+
+    @classmethod
+    def from_rgbd(cls, depth, cam_view, cam_view_proj, tanfov, targets, *, mask=None, normal=None, pixel_stride=1,
+                  max_points=200_000, depth_range=(0.0, float("inf")), mask_threshold=0.5, erode=0, **from_points_kw):
+        """A fitter that starts from its own posed RGB-D views: ``depth`` [V,1,H,W] or [V,H,W] (camera z, what ``render`` returns; 0,
+        NaN and inf are holes) is unprojected through ``cam_view`` / ``tanfov`` (``pointcloud.unproject_depth_views``: every
+        ``pixel_stride``-th row and column, foreground of ``mask`` eroded ``erode`` times when a mask is given), the colours are
+        ``targets`` at the pixels, the normals ``normal`` [V,3,H,W] (world space) or, without it, ``losses.depth_to_normal`` of the
+        depth.  The number of points is read back once, here; the trimmed cloud goes to ``from_points`` with ``from_points_kw``
+        (``K``, ``opacity``, ``scale_factor`` and the constructor's keywords).  ``mask`` and ``normal`` are the constructor's as well:
+        they supervise alpha and the normals as they would in ``SurfelFitter(...)``.  More than ``max_points`` valid pixels raise, with
+        the stride that would fit: nothing is subsampled silently."""
+        from . import cameras, losses, pointcloud
+        if not isinstance(depth, torch.Tensor) or not isinstance(targets, torch.Tensor) or not isinstance(cam_view, torch.Tensor):
+            raise TypeError("depth, cam_view and targets must be torch.Tensors")
+        if int(max_points) < 4:
+            raise ValueError("max_points must be at least 4: the initial scale needs the three nearest other points")
+        if int(pixel_stride) < 1:
+            raise ValueError("pixel_stride must be at least 1")
+        if targets.dim() != 4 or targets.shape[1] != 3 or depth.dim() not in (3, 4) or \
+                (int(depth.shape[0]), int(depth.shape[-2]), int(depth.shape[-1])) != (int(targets.shape[0]),) + tuple(targets.shape[2:]):
+            raise ValueError("targets is [V,3,H,W] and depth [V,1,H,W] or [V,H,W] of the same views")
+        cam = cameras.cameras_from_view(cam_view, tanfov)
+        if depth.device.type != "cuda":
+            raise RuntimeError("depth must be on the GPU (no CPU fallback)")
+        with torch.no_grad():
+            d4 = depth.detach().float().reshape(depth.shape[0], 1, depth.shape[-2], depth.shape[-1])
+            nrm = normal if normal is not None else losses.depth_to_normal(cam_view.detach().float().transpose(1, 2), float(tanfov), d4)
+            cloud = pointcloud.unproject_depth_views(d4, cam, mask=mask, color=targets, normal=nrm, depth_kind="z",
+                                                     depth_range=depth_range, mask_threshold=mask_threshold, erode=erode,
+                                                     pixel_stride=int(pixel_stride))
+            n = int(cloud.count.item())                      # the one host read
+        if n > int(max_points):
+            fit = int(pixel_stride)
+            while n * (int(pixel_stride) / fit) ** 2 > int(max_points):
+                fit += 1
+            raise ValueError(f"{n} valid pixels at pixel_stride={int(pixel_stride)} exceed max_points={int(max_points)}: "
+                             f"pixel_stride={fit} would give about {int(n * (int(pixel_stride) / fit) ** 2)}")
+        if n < 4:
+            raise ValueError(f"only {n} valid pixels: a fit needs at least 4 points")
+        cloud = cloud.trimmed(n)
+        extra = {k: v for k, v in (("mask", mask), ("normal", normal)) if v is not None}
+        return cls.from_points(cloud.points, cam_view, cam_view_proj, tanfov, targets, colors=cloud.colors, normals=cloud.normals,
+                               **extra, **from_points_kw)
 
     def _allocate_points(self, raw, m, v, capacity, seg_capacity=0):
         """everything whose size depends on the number of surfels: the state and its snapshot, the activated arrays, the radii, the

@@ -9,7 +9,8 @@
   * what the engine leaves for viewers: coloured point clouds as binary glTF + PLY (:1452-1464, :1742-1753), meshes as GLB / OBJ
     (utils/mesh_util.py:113-136), the surfels as a 2DGS-style PLY (nsr/gs_surfel.py:206-265).
   * the evaluation hand-off ``fps-4096.ply`` (scripts/save_pcd_from_gs.py:148-185): ``export_fps_points`` -- the one function here
-    that needs the GPU (farthest point sampling, ``gaussiananything_amd.pointcloud``).
+    that needs the GPU (farthest point sampling, ``gaussiananything_amd.pointcloud``) -- and ``export_fps_points_from_depth``, the
+    ground-truth side of the same file from posed depth views (scripts/save_pcd.py:323-403), on the GPU as well.
 
 ``gaussiananything_amd.cascade`` keeps the tensors on the device; these functions reproduce the file-based hand-off for
 interoperability with the reference scripts.
@@ -334,6 +335,43 @@ def export_fps_points(gaussians, path, K=4096, opacity_thres=0.005):
     if kept.shape[0] == 0:
         raise ValueError("no surfel reaches the opacity threshold")
     pts = sample_farthest_points(kept[None], K=K)[0][0].cpu().numpy()
+    save_points_ply(path, pts)
+    return pts
+
+
+def export_fps_points_from_depth(depth, c, path, K=4096, alpha_mask=None, depth_min=1.05, clip=XYZ_CLIP):
+    """The ground-truth hand-off ``fps-{K}.ply`` from posed depth views (scripts/save_pcd.py:323-403, ``save_pcd_from_depth``), with
+    the reference's defaults: ``depth`` [V,H,W] is the distance along the normalised ray of its g-buffers, ``c`` [V,25] the poses;
+    depths under ``depth_min`` are dropped (``depth < 1.05`` there: a depth equal to it stays), pixels whose ``alpha_mask`` [V,H,W]
+    is not exactly 1 are dropped, coordinates are clipped to ``+-clip`` with the boundary dropped, points with a coordinate of exactly
+    0 are dropped, and ``K`` farthest points starting from index 0 of what remains, in pixel order, are written as a vertex-only PLY.
+    Unprojection and sampling run on the device (``pointcloud.unproject_depth_views``, ``sample_farthest_points``: GPU only, no
+    fallback); the count is read once.  Unlike the reference, a NaN depth is dropped instead of kept as a NaN point.  Returns the
+    points, float32 [K, 3]; fewer than ``K`` remaining points leave zeros, as in ``export_fps_points``."""
+    import torch
+    from .pointcloud import sample_farthest_points, unproject_depth_views
+    as_t = lambda a: a.detach() if hasattr(a, "detach") else torch.from_numpy(np.asarray(a))
+    d, poses = as_t(depth), as_t(c)
+    if d.dim() == 4 and d.shape[1] == 1:
+        d = d[:, 0]
+    if d.dim() != 3 or poses.dim() != 2 or tuple(poses.shape) != (d.shape[0], 25):
+        raise ValueError("expected depth [V, H, W] and poses c [V, 25]")
+    d, poses = d.to("cuda", torch.float32), poses.to("cuda", torch.float32)
+    mask = None
+    if alpha_mask is not None:
+        m = as_t(alpha_mask).to("cuda")
+        if m.dim() == 4 and m.shape[1] == 1:
+            m = m[:, 0]
+        if tuple(m.shape) != tuple(d.shape):
+            raise ValueError("alpha_mask has the depth's shape")
+        mask = (m == 1).float()
+    # `depth < depth_min` is dropped and `depth == depth_min` kept: the open lower bound is the fp32 number below depth_min
+    lo = float(np.nextafter(np.float32(depth_min), np.float32(-np.inf)))
+    cloud = unproject_depth_views(d, poses, mask=mask, depth_kind="ray", depth_range=(lo, float("inf")), mask_threshold=0.5,
+                                  clip=clip, drop_zero=True).trimmed()
+    if cloud.points.shape[0] == 0:
+        raise ValueError("no pixel survives the depth, mask and clip filters")
+    pts = sample_farthest_points(cloud.points[None], K=K)[0][0].cpu().numpy()
     save_points_ply(path, pts)
     return pts
 

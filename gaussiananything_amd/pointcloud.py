@@ -14,6 +14,10 @@
                              OUR OWN definition, sign and invalid-row rules included
     surfels_from_cloud       initial 2D surfels [B,N,13] from a cloud, ``ga_pc_surfel_init``: 2DGS's distance rule for the scale, the
                              PCA frame for the rotation (``fitting.surfels_from_points`` is the single-cloud front end)
+    unproject_depth_views    posed depth views (with optional mask, colour and normal maps) -> an ordered, compacted world-space cloud,
+                             ``ga_pc_unproject`` (csrc/pc_unproject.hip): the reference's ``save_pcd_from_depth`` geometry
+                             (/root/reference/scripts/save_pcd.py:323-403), three launches, the count stays on the device
+    cloud_from_render        the same for the dict ``GaussianRenderer2DGS.render`` returns
 
 pytorch3d is absent from this image; its published behaviour is restated, parity UNPINNED ('Point clouds').  The tensors
 stay on the device and the work goes on the current stream.  There is no CPU fallback: without the HIP library, or on a CPU tensor,
@@ -403,3 +407,144 @@ def surfels_from_cloud(points: torch.Tensor, lengths=None, colors=None, normals=
     with torch.cuda.device(p.device):
         _lib.check(_lib.lib().ga_pc_surfel_init(ctypes.byref(args), _stream(p.device)), "ga_pc_surfel_init")
     return out
+
+
+# ---- point clouds from posed depth views (include/ga_pointcloud.h, csrc/pc_unproject.hip) ----------------------------------------------
+class UnprojectedCloud:
+    """What ``unproject_depth_views`` returns, everything on the device and padded to ``capacity`` rows: ``points`` [capacity,3],
+    ``colors`` and ``normals`` [capacity,3] or None, ``source`` [capacity] int32 (the pixel ``(v * H + y) * W + x`` of each row, -1 on
+    padding), ``count`` [1] int32 (the number of valid pixels, even beyond ``capacity``) and ``view_counts`` [V] int32.  Rows are in
+    ascending ``source`` order.  ``trimmed()`` does the one host read."""
+
+    __slots__ = ("points", "colors", "normals", "source", "count", "view_counts", "capacity")
+
+    def __init__(self, points, colors, normals, source, count, view_counts):
+        self.points, self.colors, self.normals, self.source = points, colors, normals, source
+        self.count, self.view_counts, self.capacity = count, view_counts, int(points.shape[0])
+
+    def trimmed(self, count=None):
+        """-> an ``UnprojectedCloud`` of exactly ``count`` rows (views of the same storage).  Reads ``count`` back -- the one host
+        synchronisation of the feature; a caller that has read it already hands it in -- and raises when the cloud did not fit its
+        capacity."""
+        n = int(self.count.item()) if count is None else int(count)
+        if n > self.capacity:
+            raise RuntimeError(f"{n} valid pixels do not fit the capacity of {self.capacity} rows: nothing past it was written")
+        cut = lambda t: t[:n] if t is not None else None
+        return UnprojectedCloud(cut(self.points), cut(self.colors), cut(self.normals), cut(self.source), self.count, self.view_counts)
+
+
+_DEPTH_KINDS = {"z": _lib.GA_PC_DEPTH_Z, "ray": _lib.GA_PC_DEPTH_RAY}
+
+
+def _view_map(t, name, V, C, H, W, like, u8=False):
+    """an optional per-view map [V,C,H,W] (C == 1: [V,H,W] as well) -> contiguous fp32 (or uint8) on the depth's device"""
+    shapes = ((V, C, H, W),) + (((V, H, W),) if C == 1 else ())
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) not in shapes:
+        raise ValueError(f"{name} is a tensor of shape {' or '.join(str(list(s)) for s in shapes)}, the depth's views")
+    if not (t.is_floating_point() or (u8 and t.dtype == torch.uint8)):
+        raise TypeError(f"{name} must be floating point" + (" or uint8" if u8 else ""))
+    if t.device != like.device:
+        raise RuntimeError(f"{name} must be on the depth's device {like.device} (no CPU fallback)")
+    t = t.detach()
+    return t.contiguous() if t.dtype == torch.uint8 else t.to(torch.float32).contiguous()
+
+
+def unproject_candidates(V: int, H: int, W: int, pixel_stride: int = 1) -> int:
+    """the pixels ``unproject_depth_views`` looks at: those with ``y % pixel_stride == 0 and x % pixel_stride == 0``"""
+    s = int(pixel_stride)
+    return int(V) * (-(-int(H) // s)) * (-(-int(W) // s))
+
+
+@torch.no_grad()
+def unproject_depth_views(depth: torch.Tensor, cameras: torch.Tensor, *, mask=None, color=None, normal=None, depth_kind: str = "z",
+                          depth_range=(0.0, float("inf")), mask_threshold: float = 0.5, erode: int = 0, clip=None,
+                          drop_zero: bool = False, pixel_stride: int = 1, capacity=None) -> UnprojectedCloud:
+    """Posed depth views -> an ordered, compacted world-space cloud on the device (``ga_pc_unproject``: three launches on the current
+    stream, no host read; the count stays in device memory).
+
+    ``depth`` [V,H,W] or [V,1,H,W]; ``cameras`` the reference's pose25 ``c`` [V,25] or ``cameras.cameras_from_view(cam_view, tanfov)``
+    [V,21]; ``mask`` (alpha) [V,H,W] or [V,1,H,W], foreground where ``mask >= mask_threshold``, eroded ``erode`` (0..4) times by the
+    3 x 3 cross; ``color`` [V,3,H,W] fp32 or uint8 (``/ 255``); ``normal`` [V,3,H,W] world space, re-normalised.  ``depth_kind``: 'z'
+    (camera z, what ``render`` returns) or 'ray' (distance along the normalised ray, the reference's g-buffers).  A pixel is valid when
+    ``depth_range[0] < depth < depth_range[1]`` (NaN and inf never are), it is foreground, with ``clip`` no coordinate reaches
+    ``+-clip`` and with ``drop_zero`` none is exactly 0; ``pixel_stride`` s looks at every s-th row and column only.  ``capacity``
+    (None: every candidate pixel) is the number of rows allocated; more valid pixels than that are reported by ``count`` alone.
+    The arithmetic is the header's, operation by operation; GPU only, no fallback."""
+    if not isinstance(depth, torch.Tensor) or depth.dim() not in (3, 4) or (depth.dim() == 4 and depth.shape[1] != 1) or depth.numel() == 0:
+        raise ValueError("depth is a [V, H, W] or [V, 1, H, W] tensor")
+    if not depth.is_floating_point():
+        raise TypeError("depth must be floating point")
+    V, H, W = int(depth.shape[0]), int(depth.shape[-2]), int(depth.shape[-1])
+    if W > _lib.GA_PC_UNPROJECT_MAX_WIDTH or V * H * W >= 2 ** 31:
+        raise ValueError(f"views are at most {_lib.GA_PC_UNPROJECT_MAX_WIDTH} wide and V * H * W stays below 2^31")
+    if depth_kind not in _DEPTH_KINDS:
+        raise ValueError("depth_kind is 'z' (camera z) or 'ray' (distance along the normalised ray)")
+    if not isinstance(cameras, torch.Tensor) or cameras.dim() != 2 or cameras.shape[0] != V or cameras.shape[1] not in (25, 21):
+        raise ValueError(f"cameras is a pose25 tensor [{V}, 25] or cameras_from_view's [{V}, 21]")
+    lo, hi = (float(x) for x in depth_range)
+    if lo != lo or hi != hi or not lo < hi:
+        raise ValueError("depth_range is (min, max) with min < max")
+    thr = float(mask_threshold)
+    if thr != thr:
+        raise ValueError("mask_threshold must not be NaN")
+    erode, stride = int(erode), int(pixel_stride)
+    if not 0 <= erode <= _lib.GA_PC_UNPROJECT_MAX_ERODE:
+        raise ValueError(f"erode must lie in [0, {_lib.GA_PC_UNPROJECT_MAX_ERODE}]")
+    if erode and mask is None:
+        raise ValueError("erode needs a mask")
+    if stride < 1:
+        raise ValueError("pixel_stride must be at least 1")
+    clip = 0.0 if clip is None else float(clip)
+    if clip != 0.0 and not (0.0 < clip < float("inf")):
+        raise ValueError("clip must be positive and finite (None: no clipping)")
+    cap = unproject_candidates(V, H, W, stride) if capacity is None else int(capacity)
+    if cap < 1 or cap >= 2 ** 31:
+        raise ValueError("capacity must lie in [1, 2^31)")
+    m = _view_map(mask, "mask", V, 1, H, W, depth) if mask is not None else None
+    col = _view_map(color, "color", V, 3, H, W, depth, u8=True) if color is not None else None
+    nrm = _view_map(normal, "normal", V, 3, H, W, depth) if normal is not None else None
+    if depth.device.type != "cuda":
+        raise RuntimeError("depth must be on the GPU (no CPU fallback)")
+    dev = depth.device
+    if cameras.device != dev:
+        raise RuntimeError(f"cameras must be on the depth's device {dev} (no CPU fallback)")
+    from . import cameras as _cameras
+    cam = (_cameras.cameras_from_pose25(cameras) if cameras.shape[1] == 25 else cameras.detach().to(torch.float32)).contiguous()
+    d = depth.detach().to(torch.float32).contiguous()
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        points = torch.empty(cap, 3, dtype=torch.float32, device=dev)
+        colors = torch.empty(cap, 3, dtype=torch.float32, device=dev) if col is not None else None
+        normals = torch.empty(cap, 3, dtype=torch.float32, device=dev) if nrm is not None else None
+        source = torch.empty(cap, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        view_counts = torch.empty(V, dtype=torch.int32, device=dev)
+        nbytes = int(L.ga_pc_unproject_workspace_bytes(V, H, W))
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        args = _lib.GaUnprojectArgs(V, H, W, _DEPTH_KINDS[depth_kind],
+                                    _lib.GA_PC_COLOR_U8 if col is not None and col.dtype == torch.uint8 else _lib.GA_PC_COLOR_F32,
+                                    erode, int(bool(drop_zero)), stride, cap, lo, hi, thr, clip, 0, d.data_ptr(), _ptr(m), _ptr(col),
+                                    _ptr(nrm), cam.data_ptr(), points.data_ptr(), _ptr(colors), _ptr(normals), source.data_ptr(),
+                                    count.data_ptr(), view_counts.data_ptr(), workspace.data_ptr(), nbytes)
+        _lib.check(L.ga_pc_unproject(ctypes.byref(args), _stream(dev)), "ga_pc_unproject")
+    return UnprojectedCloud(points, colors, normals, source, count, view_counts)
+
+
+def cloud_from_render(out: dict, cam_view: torch.Tensor, tanfov, *, batch_index: int = 0, **kw) -> UnprojectedCloud:
+    """The dict ``GaussianRenderer2DGS.render`` returns -> the cloud of ONE batch item: depth = ``out['depth']`` (camera z), mask =
+    ``out['alpha']``, colour = ``out['image']``, normal = ``out['rend_normal']``; ``cam_view`` [V,4,4] or [B,V,4,4] and ``tanfov`` as
+    ``render`` took them.  Maps of [V,C,H,W] are taken as they are, maps of [B,V,C,H,W] at ``batch_index``.  ``kw`` goes to
+    ``unproject_depth_views`` (``mask=None`` / ``color=None`` / ``normal=None`` there drop a map)."""
+    from . import cameras as _cameras
+    for k in ("depth", "alpha", "image", "rend_normal"):
+        if k not in out or not isinstance(out[k], torch.Tensor) or out[k].dim() not in (4, 5):
+            raise ValueError(f"out['{k}'] is missing or is no [V,C,H,W] / [B,V,C,H,W] tensor: out is what render returns")
+    pick = lambda t, nd: t[int(batch_index)] if t.dim() == nd + 1 else t
+    if not isinstance(cam_view, torch.Tensor) or cam_view.dim() not in (3, 4):
+        raise ValueError("cam_view is [V, 4, 4] or [B, V, 4, 4]")
+    cam = _cameras.cameras_from_view(pick(cam_view, 3), tanfov)
+    maps = dict(mask=pick(out["alpha"], 4), color=pick(out["image"], 4), normal=pick(out["rend_normal"], 4))
+    maps.update({k: kw.pop(k) for k in ("mask", "color", "normal") if k in kw})
+    if "depth_kind" in kw:
+        raise ValueError("render's depth is the camera z: depth_kind is not a choice here")
+    return unproject_depth_views(pick(out["depth"], 4), cam.to(out["depth"].device), depth_kind="z", **maps, **kw)

@@ -2,7 +2,7 @@
  * ga_pointcloud.h -- C-ABI of the MI355X-native point-cloud operations on the generation side: farthest point sampling,
  * nearest point (the building block of the Chamfer distance), the k nearest neighbours and the gradient of their squared distances;
  * and, on the neighbour lists, PCA normals and the initial 2D surfels of a fit (ga_pc_normals, ga_pc_surfel_init: the project's own
- * definitions, at the end of this file).
+ * definitions) and point clouds from posed depth views (ga_pc_unproject), both at the end of this file.
  *
  * Replaces, for a cloud the USER hands to stage 2 and for the evaluation hand-off of generated surfels,
  *     pytorch3d.ops.sample_farthest_points      (fps-xyz of the stage-2 entry, /root/reference/nsr/lsgm/flow_matching_trainer.py:1079, :1110-1134;
@@ -245,6 +245,94 @@ typedef struct GaSurfelInitArgs {
 } GaSurfelInitArgs;
 
 int ga_pc_surfel_init(const GaSurfelInitArgs *args, void *stream);
+
+/* ---- point clouds from posed depth views (csrc/pc_unproject.hip) -------------------------------------------------------------------------
+ * V views of H x W: every valid pixel becomes one world-space point, the points compacted in ascending order of their source pixel
+ * (v * H + y) * W + x -- the order of the reference's gt_pos[nonzero_mask] (/root/reference/scripts/save_pcd.py:323-403,
+ * save_pcd_from_depth; the rays of nsr/volumetric_rendering/ray_sampler.py:211-271).  The arithmetic contract above holds: fp32, every
+ * operation rounded on its own, only + - * / sqrt and comparisons, so tests/_unproject_ref.py reproduces every output bit for bit.
+ *
+ * CAMERA, 21 floats per view: [0..8] the camera-to-world rotation R, row-major; [9..11] the camera position t; [12..16] fx, fy, cx, cy,
+ * sk in the reference's normalised-intrinsics units (of a pose25 `c`: c[16], c[20], c[18], c[21], c[17]); [17..20] reserved, 0.
+ *
+ * POINT of pixel (x, y) of view v with depth z, F(.) the conversion of an integer to fp32:
+ *     u  = F(x) * (1 / F(W)) + 0.5 / F(W);   v' = F(y) * (1 / F(H)) + 0.5 / F(H)                   (the reference's create_uv)
+ *     xl = (((u - cx) + (cy * sk) / fy) - (sk * v') / fy) / fx;   yl = (v' - cy) / fy
+ *     d_a = (R_a0 * xl + R_a1 * yl) + R_a2                                               a = x, y, z
+ *     depth_kind GA_PC_DEPTH_RAY only:  l = max(sqrt((dx * dx + dy * dy) + dz * dz), 1e-12);  d_a = d_a / l
+ *     p_a = t_a + z * d_a
+ *     clip > 0:  p_a = min(max(p_a, -clip), clip)
+ * The reference forms d as (R [xl, yl, 1] + t) - t with a matrix product; the order above is ours and is the specification.
+ *
+ * VALID is a pixel for which all of these hold (a NaN fails every comparison it meets):
+ *     y % pixel_stride == 0 and x % pixel_stride == 0
+ *     depth_min < z and z < depth_max
+ *     mask given: the pixel is foreground, mask >= mask_threshold, and with erode = e > 0 so is every pixel of the image within
+ *         |dx| + |dy| <= e of it: e iterations of the 3 x 3 cross erosion (the reference's kornia call, commented out at
+ *         save_pcd.py:346-356), pixels outside the image never eroding anything (kornia's geodesic border).  The erosion runs on the full
+ *         image, whatever pixel_stride is.
+ *     clip > 0: no |p_a| == clip after the clamp (save_pcd.py:389-390: the boundary is dropped, and with it everything beyond it)
+ *     drop_zero: no p_a == 0 (:394)
+ *
+ * OUTPUTS.  Row r < min(count, capacity) holds the r-th valid pixel in ascending source order: points[r] = p; colors[r] = the three
+ * planes of color at the pixel, a uint8 colour converted as F(c) / 255; normals[r] = n / l with l = sqrt((nx * nx + ny * ny) + nz * nz),
+ * (0, 0, 1) unless l > 0; source[r] = (v * H + y) * W + x.  Rows min(count, capacity) .. capacity - 1 hold zeros and source -1.
+ * count[0] is the number of valid pixels even when it exceeds capacity (the only report of overflow), view_counts[v] that of view v.
+ *
+ * LAUNCHES: three, ordered by the stream, no workgroup waits for another, no atomics.  A workgroup owns a band of
+ * rows_per_block = clamp(GA_PC_UNPROJECT_TILE_PIXELS / W, 1, H) full rows of one view, so workgroup order is source order.
+ *     1 flag     validity of every pixel of the band (the thresholded mask staged in LDS with an erode-wide halo when erode > 0), one
+ *                byte per pixel and the band's count to the workspace
+ *     2 scan     ONE workgroup walks the band counts GA_PC_UNPROJECT_THREADS at a time, leaves exclusive offsets, count and view_counts
+ *     3 scatter  ranks the band's flags, computes the point of a valid pixel AGAIN and writes its row; further workgroups write the padding
+ * The point is recomputed in the scatter pass, not stored by the flag pass: on gfx950 the lift to the point is about 150 VALU
+ * instructions per 64 valid pixels' wave (four divisions, and with ray depth three more and a square root, are most of them) against 24 bytes of extra
+ * memory traffic per pixel for a stored point, in a scatter launch that is bound by memory traffic. */
+#define GA_PC_DEPTH_Z 0    /* depth is the camera-space z: what the rasterizer's `depth` map holds          */
+#define GA_PC_DEPTH_RAY 1  /* depth is the distance along the normalised ray: what the reference's g-buffers hold */
+#define GA_PC_COLOR_F32 0
+#define GA_PC_COLOR_U8 1
+#define GA_PC_UNPROJECT_THREADS 256
+#define GA_PC_UNPROJECT_TILE_PIXELS 1024
+#define GA_PC_UNPROJECT_MAX_WIDTH 4096
+#define GA_PC_UNPROJECT_MAX_ERODE 4
+#define GA_PC_CAMERA_FLOATS 21
+
+typedef struct GaUnprojectArgs {
+    int32_t num_views;        /* V >= 1, V * H * W < 2^31                                                  */
+    int32_t height;           /* H >= 1                                                                    */
+    int32_t width;            /* W, 1 .. GA_PC_UNPROJECT_MAX_WIDTH                                         */
+    int32_t depth_kind;       /* GA_PC_DEPTH_*                                                             */
+    int32_t color_kind;       /* GA_PC_COLOR_*: the element type of `color`                                */
+    int32_t erode;            /* 0 .. GA_PC_UNPROJECT_MAX_ERODE; ignored without a mask                    */
+    int32_t drop_zero;        /* 0 or 1                                                                    */
+    int32_t pixel_stride;     /* >= 1                                                                      */
+    int32_t capacity;         /* rows of the outputs, >= 1                                                 */
+    float depth_min;          /* not NaN                                                                   */
+    float depth_max;          /* not NaN; +inf = no upper bound (an infinite depth is still invalid)       */
+    float mask_threshold;     /* not NaN                                                                   */
+    float clip;               /* 0 = off, else positive and finite                                         */
+    int32_t reserved;         /* 0                                                                         */
+    const float *depth;       /* [V,H,W]                                                                   */
+    const float *mask;        /* [V,H,W] or NULL                                                           */
+    const void *color;        /* [V,3,H,W] fp32 or uint8, or NULL                                          */
+    const float *normal;      /* [V,3,H,W] world space, or NULL                                            */
+    const float *cameras;     /* [V,GA_PC_CAMERA_FLOATS]                                                   */
+    float *points;            /* [capacity,3]                                                              */
+    float *colors;            /* [capacity,3]: given exactly when `color` is                               */
+    float *normals;           /* [capacity,3]: given exactly when `normal` is                              */
+    int32_t *source;          /* [capacity]                                                                */
+    int32_t *count;           /* [1]                                                                       */
+    int32_t *view_counts;     /* [V]                                                                       */
+    void *workspace;          /* ga_pc_unproject_workspace_bytes(V, H, W) bytes, 16-byte aligned           */
+    size_t workspace_bytes;
+} GaUnprojectArgs;
+
+/* host: bytes of workspace ga_pc_unproject needs, 0 for a shape it rejects */
+size_t ga_pc_unproject_workspace_bytes(int32_t num_views, int32_t height, int32_t width);
+/* GA_OK, GA_ERR_NULL_ARG, GA_ERR_BAD_SHAPE (the limits above), GA_ERR_BAD_FLAGS (a kind, erode, drop_zero, pixel_stride, reserved or a
+ * scalar out of its range), GA_ERR_WORKSPACE or GA_ERR_LAUNCH */
+int ga_pc_unproject(const GaUnprojectArgs *args, void *stream);
 
 #ifdef __cplusplus
 }
