@@ -155,6 +155,28 @@ class GaUnprojectArgs(ctypes.Structure):
                                                "count", "view_counts", "workspace")] + [("workspace_bytes", ctypes.c_size_t)]
 
 
+_PC_FILTER_CLOUD = ("in_count", "points", "colors", "normals", "source")
+_PC_FILTER_OUT = ("out_points", "out_colors", "out_normals", "out_source", "kept_rows", "count", "view_counts")
+
+
+class GaFilterViewsArgs(ctypes.Structure):
+    """include/ga_pointcloud.h: GaFilterViewsArgs"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("rows", "capacity", "num_views", "height", "width", "depth_kind", "window", "min_support",
+                                              "max_conflicts", "carve")] + \
+               [(n, ctypes.c_float) for n in ("depth_min", "depth_max", "mask_threshold", "tol_abs", "tol_rel")] + \
+               [("reserved", ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in _PC_FILTER_CLOUD + ("depth", "mask", "cameras") + _PC_FILTER_OUT +
+                ("support", "conflicts", "workspace")] + [("workspace_bytes", ctypes.c_size_t)]
+
+
+class GaVoxelThinArgs(ctypes.Structure):
+    """include/ga_pointcloud.h: GaVoxelThinArgs"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("rows", "capacity", "keep", "num_views", "view_pixels", "flags")] + \
+               [("origin", ctypes.c_float * 3), ("voxel_size", ctypes.c_float), ("table_slots", ctypes.c_int64)] + \
+               [(n, ctypes.c_void_p) for n in _PC_FILTER_CLOUD + _PC_FILTER_OUT + ("multiplicity", "dropped", "workspace")] + \
+               [("workspace_bytes", ctypes.c_size_t)]
+
+
 class GaPhotoLossArgs(ctypes.Structure):
     """include/ga_loss.h: GaPhotoLossArgs"""
     _fields_ = [("num_images", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
@@ -261,6 +283,8 @@ GA_PC_NORMALS_SWEEPS, GA_PC_NORMALS_MIN_K, GA_PC_SURFEL_MIN_K, GA_PC_SURFEL_FLOA
 GA_PC_DEPTH_Z, GA_PC_DEPTH_RAY, GA_PC_COLOR_F32, GA_PC_COLOR_U8 = 0, 1, 0, 1
 GA_PC_UNPROJECT_THREADS, GA_PC_UNPROJECT_TILE_PIXELS, GA_PC_UNPROJECT_MAX_WIDTH, GA_PC_UNPROJECT_MAX_ERODE = 256, 1024, 4096, 4
 GA_PC_CAMERA_FLOATS = 21
+GA_PC_FILTER_THREADS, GA_PC_FILTER_BAND_ROWS, GA_PC_FILTER_MAX_ROWS = 256, 1024, 1 << 30
+GA_PC_VOXEL_FIRST, GA_PC_VOXEL_CENTER, GA_PC_VOXEL_MAX_INDEX, GA_PC_VOXEL_WAVE_MERGE = 0, 1, (1 << 20) - 1, 1
 
 EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspace_layout2", "ga_surfel_forward", "ga_surfel_postprocess",
            "ga_surfel_backward", "ga_surfel_backward_scratch_bytes", "ga_surfel_store_policy",
@@ -268,6 +292,7 @@ EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspa
            "ga_pc_fps", "ga_pc_fps_plan", "ga_pc_fps_workspace_bytes", "ga_pc_nearest",
            "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward", "ga_pc_normals", "ga_pc_normals_plan", "ga_pc_surfel_init",
            "ga_pc_unproject", "ga_pc_unproject_workspace_bytes",
+           "ga_pc_filter_views", "ga_pc_filter_views_workspace_bytes", "ga_pc_voxel_thin", "ga_pc_voxel_thin_workspace_bytes",
            "ga_photo_loss_plan", "ga_photo_loss_workspace_bytes", "ga_photo_loss_forward", "ga_photo_loss_backward",
            "ga_geo_loss_plan", "ga_geo_loss_workspace_bytes", "ga_geo_loss_forward", "ga_geo_loss_backward",
            "ga_fit_plan", "ga_fit_activate", "ga_fit_pack_grads", "ga_fit_adam", "ga_fit_advance", "ga_fit_select_views",
@@ -353,6 +378,14 @@ def lib():
         L.ga_pc_unproject.argtypes = [ctypes.POINTER(GaUnprojectArgs), ctypes.c_void_p]
         L.ga_pc_unproject_workspace_bytes.restype = ctypes.c_size_t
         L.ga_pc_unproject_workspace_bytes.argtypes = [ctypes.c_int32] * 3
+        L.ga_pc_filter_views.restype = ctypes.c_int
+        L.ga_pc_filter_views.argtypes = [ctypes.POINTER(GaFilterViewsArgs), ctypes.c_void_p]
+        L.ga_pc_filter_views_workspace_bytes.restype = ctypes.c_size_t
+        L.ga_pc_filter_views_workspace_bytes.argtypes = [ctypes.c_int32]
+        L.ga_pc_voxel_thin.restype = ctypes.c_int
+        L.ga_pc_voxel_thin.argtypes = [ctypes.POINTER(GaVoxelThinArgs), ctypes.c_void_p]
+        L.ga_pc_voxel_thin_workspace_bytes.restype = ctypes.c_size_t
+        L.ga_pc_voxel_thin_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64]
         L.ga_photo_loss_plan.restype = ctypes.c_int
         L.ga_photo_loss_plan.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(GaPhotoLossPlan)]
         L.ga_photo_loss_workspace_bytes.restype = ctypes.c_size_t

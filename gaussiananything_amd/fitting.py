@@ -478,7 +478,8 @@ class SurfelFitter:
 
     @classmethod
     def from_rgbd(cls, depth, cam_view, cam_view_proj, tanfov, targets, *, mask=None, normal=None, pixel_stride=1,
-                  max_points=200_000, depth_range=(0.0, float("inf")), mask_threshold=0.5, erode=0, **from_points_kw):
+                  max_points=200_000, depth_range=(0.0, float("inf")), mask_threshold=0.5, erode=0, consistency=None,
+                  voxel_size=None, **from_points_kw):
         """A fitter that starts from its own posed RGB-D views: ``depth`` [V,1,H,W] or [V,H,W] (camera z, what ``render`` returns; 0,
         NaN and inf are holes) is unprojected through ``cam_view`` / ``tanfov`` (``pointcloud.unproject_depth_views``: every
         ``pixel_stride``-th row and column, foreground of ``mask`` eroded ``erode`` times when a mask is given), the colours are
@@ -486,8 +487,18 @@ class SurfelFitter:
         depth.  The number of points is read back once, here; the trimmed cloud goes to ``from_points`` with ``from_points_kw``
         (``K``, ``opacity``, ``scale_factor`` and the constructor's keywords).  ``mask`` and ``normal`` are the constructor's as well:
         they supervise alpha and the normals as they would in ``SurfelFitter(...)``.  More than ``max_points`` valid pixels raise, with
-        the stride that would fit: nothing is subsampled silently."""
+        the stride that would fit: nothing is subsampled silently.
+
+        ``consistency`` (None: off; True, or a dict of ``pointcloud.filter_view_consistency``'s keywords) drops the points that the
+        depth maps of the other views contradict -- the same depth, mask, cameras, ``depth_range`` and ``mask_threshold``;
+        ``voxel_size`` (None: off) then keeps one point per cell of that size (``pointcloud.voxel_thin``, the point nearest each
+        cell's centre), which thins where views overlap and keeps what only one view sees.  Both run on the device before the one
+        count read, and ``max_points`` applies to what they leave."""
         from . import cameras, losses, pointcloud
+        if consistency is not None and consistency is not True and not isinstance(consistency, dict):
+            raise TypeError("consistency is None, True or a dict of filter_view_consistency's keywords")
+        if voxel_size is not None and not (0.0 < float(voxel_size) < float("inf")):
+            raise ValueError("voxel_size must be positive and finite (None: no thinning)")
         if not isinstance(depth, torch.Tensor) or not isinstance(targets, torch.Tensor) or not isinstance(cam_view, torch.Tensor):
             raise TypeError("depth, cam_view and targets must be torch.Tensors")
         if int(max_points) < 4:
@@ -506,13 +517,21 @@ class SurfelFitter:
             cloud = pointcloud.unproject_depth_views(d4, cam, mask=mask, color=targets, normal=nrm, depth_kind="z",
                                                      depth_range=depth_range, mask_threshold=mask_threshold, erode=erode,
                                                      pixel_stride=int(pixel_stride))
+            if consistency is not None:
+                rule = dict(depth_range=depth_range, mask_threshold=mask_threshold)
+                rule.update(consistency if isinstance(consistency, dict) else {})
+                cloud = pointcloud.filter_view_consistency(cloud, d4, cam, mask=mask, depth_kind="z", **rule)
+            if voxel_size is not None:
+                cloud = pointcloud.voxel_thin(cloud, float(voxel_size))
             n = int(cloud.count.item())                      # the one host read
         if n > int(max_points):
             fit = int(pixel_stride)
             while n * (int(pixel_stride) / fit) ** 2 > int(max_points):
                 fit += 1
             raise ValueError(f"{n} valid pixels at pixel_stride={int(pixel_stride)} exceed max_points={int(max_points)}: "
-                             f"pixel_stride={fit} would give about {int(n * (int(pixel_stride) / fit) ** 2)}")
+                             f"pixel_stride={fit} would give about {int(n * (int(pixel_stride) / fit) ** 2)}"
+                             + (f"; a voxel_size larger than {float(voxel_size)} thins further" if voxel_size is not None else
+                                "; voxel_size= keeps one point per cell of space instead of thinning every view blindly"))
         if n < 4:
             raise ValueError(f"only {n} valid pixels: a fit needs at least 4 points")
         cloud = cloud.trimmed(n)

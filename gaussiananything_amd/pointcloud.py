@@ -18,6 +18,10 @@
                              ``ga_pc_unproject`` (csrc/pc_unproject.hip): the reference's ``save_pcd_from_depth`` geometry
                              (/root/reference/scripts/save_pcd.py:323-403), three launches, the count stays on the device
     cloud_from_render        the same for the dict ``GaussianRenderer2DGS.render`` returns
+    filter_view_consistency  keeps the points of such a cloud (or of any cloud) that the depth maps of the other views support and do
+                             not contradict, ``ga_pc_filter_views`` (csrc/pc_filter.hip): OUR OWN rule, three launches, no host read
+    voxel_thin               one measured point per occupied cell of a grid, ``ga_pc_voxel_thin``: a hash table filled with integer
+                             atomics, the result a function of the input alone; five launches, no host read
 
 pytorch3d is absent from this image; its published behaviour is restated, parity UNPINNED ('Point clouds').  The tensors
 stay on the device and the work goes on the current stream.  There is no CPU fallback: without the HIP library, or on a CPU tensor,
@@ -528,6 +532,193 @@ def unproject_depth_views(depth: torch.Tensor, cameras: torch.Tensor, *, mask=No
                                     count.data_ptr(), view_counts.data_ptr(), workspace.data_ptr(), nbytes)
         _lib.check(L.ga_pc_unproject(ctypes.byref(args), _stream(dev)), "ga_pc_unproject")
     return UnprojectedCloud(points, colors, normals, source, count, view_counts)
+
+
+# ---- cross-view consistency filter and voxel thinning (include/ga_pointcloud.h, csrc/pc_filter.hip) --------------------------------------
+class FilteredCloud(UnprojectedCloud):
+    """What ``filter_view_consistency`` and ``voxel_thin`` return: an ``UnprojectedCloud`` (``source`` and ``view_counts`` None for a
+    cloud that came without ``source``) plus ``kept_rows`` [capacity] int32 (the input row of every row, -1 on padding) and, from the
+    filter with ``return_votes``, ``support`` / ``conflicts`` [input rows] uint8, or, from the thinning, ``multiplicity`` [capacity]
+    int32 (the live input rows in the row's cell) and ``dropped`` [1] int32 (rows outside the grid).  ``trimmed()`` cuts the
+    per-row outputs; the votes are per INPUT row and stay whole."""
+
+    __slots__ = ("kept_rows", "multiplicity", "support", "conflicts", "dropped")
+
+    def __init__(self, points, colors, normals, source, count, view_counts, kept_rows, multiplicity=None, support=None, conflicts=None,
+                 dropped=None):
+        super().__init__(points, colors, normals, source, count, view_counts)
+        self.kept_rows, self.multiplicity, self.support, self.conflicts, self.dropped = kept_rows, multiplicity, support, conflicts, dropped
+
+    def trimmed(self, count=None):
+        n = int(self.count.item()) if count is None else int(count)
+        if n > self.capacity:
+            raise RuntimeError(f"{n} kept rows do not fit the capacity of {self.capacity} rows: nothing past it was written")
+        cut = lambda t: t[:n] if t is not None else None
+        return FilteredCloud(cut(self.points), cut(self.colors), cut(self.normals), cut(self.source), self.count, self.view_counts,
+                             cut(self.kept_rows), cut(self.multiplicity), self.support, self.conflicts, self.dropped)
+
+
+_VOXEL_KEEP = {"first": _lib.GA_PC_VOXEL_FIRST, "center": _lib.GA_PC_VOXEL_CENTER}
+VOXEL_WAVE_MERGE = True      # the measured choice (profiles/pc_filter_bench.txt); the outputs are the same either way
+
+
+def _filter_input(cloud, colors, normals, what):
+    """an ``UnprojectedCloud`` (trimmed or not) or a [N,3] tensor -> (points, colors, normals, source, in_count), fp32 and contiguous"""
+    if isinstance(cloud, UnprojectedCloud):
+        if colors is not None or normals is not None:
+            raise ValueError(f"{what}: colors and normals go with a [N, 3] tensor; an UnprojectedCloud brings its own")
+        pts, colors, normals, source, in_count = cloud.points, cloud.colors, cloud.normals, cloud.source, cloud.count
+    else:
+        pts, source, in_count = cloud, None, None
+    if not isinstance(pts, torch.Tensor) or pts.dim() != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+        raise ValueError(f"{what}: the cloud is an UnprojectedCloud or a [N, 3] tensor with N >= 1")
+    if not pts.is_floating_point():
+        raise TypeError(f"{what}: the points must be floating point")
+    if pts.shape[0] > _lib.GA_PC_FILTER_MAX_ROWS:
+        raise ValueError(f"{what}: at most {_lib.GA_PC_FILTER_MAX_ROWS} rows")
+    f32 = lambda t: t.detach().to(torch.float32).contiguous()
+    for name, t in (("colors", colors), ("normals", normals)):
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(pts.shape) or t.device != pts.device or
+                              not t.is_floating_point()):
+            raise ValueError(f"{what}: {name} is a floating-point [N, 3] tensor on the cloud's device")
+    if pts.device.type != "cuda":
+        raise RuntimeError(f"{what}: the cloud must be on the GPU (no CPU fallback)")
+    return f32(pts), f32(colors) if colors is not None else None, f32(normals) if normals is not None else None, source, in_count
+
+
+def _filter_outputs(cap, dev, colors, normals, source, num_views):
+    e = lambda *shape, dtype=torch.float32: torch.empty(*shape, dtype=dtype, device=dev)
+    return dict(points=e(cap, 3), colors=e(cap, 3) if colors is not None else None, normals=e(cap, 3) if normals is not None else None,
+                source=e(cap, dtype=torch.int32) if source is not None else None, kept_rows=e(cap, dtype=torch.int32),
+                count=e(1, dtype=torch.int32),
+                view_counts=e(num_views, dtype=torch.int32) if source is not None and num_views else None)
+
+
+def _capacity(capacity, rows):
+    cap = rows if capacity is None else int(capacity)
+    if cap < 1 or cap >= 2 ** 31:
+        raise ValueError("capacity must lie in [1, 2^31)")
+    return cap
+
+
+@torch.no_grad()
+def filter_view_consistency(cloud, depth: torch.Tensor, cameras: torch.Tensor, *, mask=None, depth_kind: str = "z",
+                            depth_range=(0.0, float("inf")), mask_threshold: float = 0.5, tolerance=(0.0, 0.01), window: int = 1,
+                            min_support: int = 1, max_conflicts: int = 0, carve: bool = False, capacity=None,
+                            return_votes: bool = False) -> FilteredCloud:
+    """Keep the points of ``cloud`` that the depth maps of the OTHER views agree with (``ga_pc_filter_views``: three launches on the
+    current stream, no host read).
+
+    ``cloud`` is an ``UnprojectedCloud`` (trimmed or not: its ``count`` is read on the device, its ``source`` names each point's own
+    view, which does not vote) or a [N,3] tensor (a foreign cloud: every view votes).  ``depth`` [V,H,W] or [V,1,H,W], ``mask`` and
+    ``cameras`` (pose25 [V,25] or [V,21]) are as in ``unproject_depth_views``; a map pixel is surface when ``depth_range[0] < z <
+    depth_range[1]`` and, with a mask, ``mask >= mask_threshold``.  Every point is projected into every other view (nearest pixel) and
+    compared with the smallest and largest surface depth of the ``(2 window + 1)^2`` pixels around it, ``tolerance`` = (absolute,
+    relative): within them and on a surface pixel it is SUPPORTED; in front of a window that is all surface it is in CONFLICT, and with
+    ``carve`` also where the window is all empty; behind the surface (occluded), on a silhouette, outside the image or behind the
+    camera the view says nothing.  A point stays when ``support >= min_support and conflicts <= max_conflicts``; the survivors keep
+    their order.  ``capacity`` (None: the input's rows) is the number of rows allocated.  ``return_votes`` adds the per-input-row
+    ``support`` and ``conflicts`` (uint8, saturated).  The arithmetic is the header's, operation by operation; GPU only, no fallback."""
+    what = "filter_view_consistency"
+    if not isinstance(depth, torch.Tensor) or depth.dim() not in (3, 4) or (depth.dim() == 4 and depth.shape[1] != 1) or depth.numel() == 0:
+        raise ValueError("depth is a [V, H, W] or [V, 1, H, W] tensor")
+    if not depth.is_floating_point():
+        raise TypeError("depth must be floating point")
+    V, H, W = int(depth.shape[0]), int(depth.shape[-2]), int(depth.shape[-1])
+    if V * H * W >= 2 ** 31:
+        raise ValueError("V * H * W stays below 2^31")
+    if depth_kind not in _DEPTH_KINDS:
+        raise ValueError("depth_kind is 'z' (camera z) or 'ray' (distance along the normalised ray)")
+    if not isinstance(cameras, torch.Tensor) or cameras.dim() != 2 or cameras.shape[0] != V or cameras.shape[1] not in (25, 21):
+        raise ValueError(f"cameras is a pose25 tensor [{V}, 25] or cameras_from_view's [{V}, 21]")
+    lo, hi = (float(x) for x in depth_range)
+    if lo != lo or hi != hi or not lo < hi:
+        raise ValueError("depth_range is (min, max) with min < max")
+    thr = float(mask_threshold)
+    if thr != thr:
+        raise ValueError("mask_threshold must not be NaN")
+    tol_abs, tol_rel = (float(x) for x in tolerance)
+    if not (0.0 <= tol_abs < float("inf") and 0.0 <= tol_rel < float("inf")):
+        raise ValueError("tolerance is (absolute, relative), both finite and not negative")
+    if int(window) not in (0, 1):
+        raise ValueError("window is 0 (the nearest pixel) or 1 (the 3 x 3 pixels around it)")
+    if int(min_support) < 0 or int(max_conflicts) < 0:
+        raise ValueError("min_support and max_conflicts must not be negative")
+    pts, colors, normals, source, in_count = _filter_input(cloud, None, None, what)
+    rows = int(pts.shape[0])
+    cap = _capacity(capacity, rows)
+    dev = pts.device
+    if depth.device != dev or cameras.device != dev:
+        raise RuntimeError(f"depth and cameras must be on the cloud's device {dev} (no CPU fallback)")
+    m = _view_map(mask, "mask", V, 1, H, W, depth) if mask is not None else None
+    from . import cameras as _cameras
+    cam = (_cameras.cameras_from_pose25(cameras) if cameras.shape[1] == 25 else cameras.detach().to(torch.float32)).contiguous()
+    d = depth.detach().to(torch.float32).contiguous()
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        o = _filter_outputs(cap, dev, colors, normals, source, V)
+        sup = torch.empty(rows, dtype=torch.uint8, device=dev) if return_votes else None
+        con = torch.empty(rows, dtype=torch.uint8, device=dev) if return_votes else None
+        nbytes = int(L.ga_pc_filter_views_workspace_bytes(rows))
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        args = _lib.GaFilterViewsArgs(rows, cap, V, H, W, _DEPTH_KINDS[depth_kind], int(window), int(min_support), int(max_conflicts),
+                                      int(bool(carve)), lo, hi, thr, tol_abs, tol_rel, 0, _ptr(in_count), pts.data_ptr(), _ptr(colors),
+                                      _ptr(normals), _ptr(source), d.data_ptr(), _ptr(m), cam.data_ptr(), o["points"].data_ptr(),
+                                      _ptr(o["colors"]), _ptr(o["normals"]), _ptr(o["source"]), o["kept_rows"].data_ptr(),
+                                      o["count"].data_ptr(), _ptr(o["view_counts"]), _ptr(sup), _ptr(con), workspace.data_ptr(), nbytes)
+        _lib.check(L.ga_pc_filter_views(ctypes.byref(args), _stream(dev)), "ga_pc_filter_views")
+    return FilteredCloud(o["points"], o["colors"], o["normals"], o["source"], o["count"], o["view_counts"], o["kept_rows"],
+                         support=sup, conflicts=con)
+
+
+@torch.no_grad()
+def voxel_thin(cloud, voxel_size: float, *, origin=(0.0, 0.0, 0.0), keep: str = "center", colors=None, normals=None, capacity=None,
+               view_pixels=None, wave_merge: bool = VOXEL_WAVE_MERGE) -> FilteredCloud:
+    """One point per occupied cell of the grid of ``voxel_size`` cells anchored at ``origin`` (``ga_pc_voxel_thin``: five launches on
+    the current stream, no host read).
+
+    ``cloud`` is an ``UnprojectedCloud`` (trimmed or not, with its own colours, normals and source) or a [N,3] tensor with optional
+    ``colors`` / ``normals`` [N,3].  The point kept of a cell is a MEASURED one with its own colour and normal -- ``keep='center'``:
+    the nearest to the cell's centre, ``'first'``: the first in input order; ties go to the lowest row -- never an average, so the
+    result is a function of the input alone.  The survivors keep their order.  A row with a non-finite coordinate or more than 2^20 - 1
+    cells from the origin is dropped and counted in ``dropped``.  ``multiplicity`` is the number of input rows in each kept row's cell.
+    ``view_pixels`` (H * W of the views ``source`` names) asks for ``view_counts``; without it they are None.  ``capacity`` (None: the
+    input's rows) is the number of rows allocated.  ``wave_merge`` inserts neighbouring rows of one cell into the table once (the
+    same outputs, another speed).  GPU only, no fallback."""
+    what = "voxel_thin"
+    vs = float(voxel_size)
+    if not (0.0 < vs < float("inf")):
+        raise ValueError("voxel_size must be positive and finite")
+    org = [float(x) for x in origin]
+    if len(org) != 3 or not all(abs(x) < float("inf") for x in org):
+        raise ValueError("origin is three finite numbers")
+    if keep not in _VOXEL_KEEP:
+        raise ValueError("keep is 'center' (the point nearest the cell's centre) or 'first' (the first in input order)")
+    num_views = 0
+    if view_pixels is not None:
+        if not isinstance(cloud, UnprojectedCloud) or cloud.view_counts is None or int(view_pixels) < 1:
+            raise ValueError("view_pixels (>= 1) goes with an UnprojectedCloud that has view_counts")
+        num_views = int(cloud.view_counts.shape[0])
+    pts, colors, normals, source, in_count = _filter_input(cloud, colors, normals, what)
+    rows = int(pts.shape[0])
+    cap = _capacity(capacity, rows)
+    dev = pts.device
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        o = _filter_outputs(cap, dev, colors, normals, source, num_views)
+        mult = torch.empty(cap, dtype=torch.int32, device=dev)
+        dropped = torch.empty(1, dtype=torch.int32, device=dev)
+        nbytes = int(L.ga_pc_voxel_thin_workspace_bytes(rows, 0))
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        args = _lib.GaVoxelThinArgs(rows, cap, _VOXEL_KEEP[keep], num_views, int(view_pixels) if num_views else 0,
+                                    _lib.GA_PC_VOXEL_WAVE_MERGE if wave_merge else 0,
+                                    (ctypes.c_float * 3)(*org), vs, 0, _ptr(in_count), pts.data_ptr(), _ptr(colors), _ptr(normals),
+                                    _ptr(source), o["points"].data_ptr(), _ptr(o["colors"]), _ptr(o["normals"]), _ptr(o["source"]),
+                                    o["kept_rows"].data_ptr(), o["count"].data_ptr(), _ptr(o["view_counts"]), mult.data_ptr(),
+                                    dropped.data_ptr(), workspace.data_ptr(), nbytes)
+        _lib.check(L.ga_pc_voxel_thin(ctypes.byref(args), _stream(dev)), "ga_pc_voxel_thin")
+    return FilteredCloud(o["points"], o["colors"], o["normals"], o["source"], o["count"], o["view_counts"], o["kept_rows"],
+                         multiplicity=mult, dropped=dropped)
 
 
 def cloud_from_render(out: dict, cam_view: torch.Tensor, tanfov, *, batch_index: int = 0, **kw) -> UnprojectedCloud:

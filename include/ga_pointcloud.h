@@ -2,7 +2,8 @@
  * ga_pointcloud.h -- C-ABI of the MI355X-native point-cloud operations on the generation side: farthest point sampling,
  * nearest point (the building block of the Chamfer distance), the k nearest neighbours and the gradient of their squared distances;
  * and, on the neighbour lists, PCA normals and the initial 2D surfels of a fit (ga_pc_normals, ga_pc_surfel_init: the project's own
- * definitions) and point clouds from posed depth views (ga_pc_unproject), both at the end of this file.
+ * definitions), point clouds from posed depth views (ga_pc_unproject) and their cross-view consistency filter and voxel thinning
+ * (ga_pc_filter_views, ga_pc_voxel_thin), all at the end of this file.
  *
  * Replaces, for a cloud the USER hands to stage 2 and for the evaluation hand-off of generated surfels,
  *     pytorch3d.ops.sample_farthest_points      (fps-xyz of the stage-2 entry, /root/reference/nsr/lsgm/flow_matching_trainer.py:1079, :1110-1134;
@@ -333,6 +334,144 @@ size_t ga_pc_unproject_workspace_bytes(int32_t num_views, int32_t height, int32_
 /* GA_OK, GA_ERR_NULL_ARG, GA_ERR_BAD_SHAPE (the limits above), GA_ERR_BAD_FLAGS (a kind, erode, drop_zero, pixel_stride, reserved or a
  * scalar out of its range), GA_ERR_WORKSPACE or GA_ERR_LAUNCH */
 int ga_pc_unproject(const GaUnprojectArgs *args, void *stream);
+
+/* ---- cross-view consistency filter and voxel thinning of a cloud (csrc/pc_filter.hip) ----------------------------------------------------
+ * Two ordered compactions of a cloud of `rows` rows, with the arithmetic contract above (fp32, every operation rounded on its own, only
+ * + - * / sqrt floor and comparisons), so tests/_pc_filter_ref.py reproduces every output bit for bit.
+ *
+ * COMMON.  in_count is a device int32 or NULL (= every row is live): only rows r < min(max(in_count[0], 0), rows) are live, read on the
+ * device, so an untrimmed ga_pc_unproject result goes straight in.  points [rows,3] is required; colors, normals [rows,3] and source
+ * [rows] are optional, each given exactly when its output is.  Every output has `capacity` rows; the kept rows come in ascending input
+ * order, row j < min(count, capacity) a copy of input row kept_rows[j]; rows min(count, capacity) .. capacity - 1 hold zeros, source -1
+ * and kept_rows -1.  count[0] is the number of kept rows even beyond capacity (the only report of overflow).  view_counts [num_views]
+ * (optional, needs source) counts the kept rows, those beyond capacity included, by source / (H * W); a kept row whose source is
+ * negative or names no view is counted nowhere.
+ *
+ * COMPACTION (both calls): a workgroup of GA_PC_FILTER_THREADS lanes owns a band of GA_PC_FILTER_BAND_ROWS consecutive rows.
+ *     flag     one flag byte per row and the band's count to the workspace (the filter's flag pass is its voting kernel)
+ *     scan     ONE workgroup walks the band counts GA_PC_FILTER_THREADS at a time with a register carry, leaves exclusive offsets and
+ *              count, and zeroes view_counts
+ *     scatter  ranks the flags by ballot and popcount, copies the rows and adds them to view_counts (counted in registers, one integer
+ *              atomic per view and workgroup for an ordered cloud); further workgroups write the padding
+ * No workgroup waits for another, nothing spins, phases are separate launches ordered by the stream; no host read, so both calls can be
+ * captured into a graph.
+ *
+ * ga_pc_filter_views: every live point p votes in every view u except its own, source[r] / (H * W), when source is given and
+ * source[r] >= 0.  Cameras are the 21 floats of ga_pc_unproject; a map pixel is SURFACE when depth_min < z < depth_max and, with a mask,
+ * mask >= mask_threshold, otherwise EMPTY (a NaN fails every comparison it meets).
+ *     1  e = p - t;  q_x = (R_00 * e_x + R_10 * e_y) + R_20 * e_z, q_y with column 1 of R, q_z with column 2; skipped unless q_z > 0
+ *     2  xl = q_x / q_z;  yl = q_y / q_z;  v' = yl * fy + cy;  u' = ((xl * fx + cx) - (cy * sk) / fy) + (sk * v') / fy
+ *     3  a = u' * F(W);  b = v' * F(H);  skipped unless 0 <= a < F(W) and 0 <= b < F(H);  x = (int)a, y = (int)b (nearest pixel)
+ *     4  d = q_z (GA_PC_DEPTH_Z) or sqrt((q_x * q_x + q_y * q_y) + q_z * q_z) (GA_PC_DEPTH_RAY)
+ *     5  the window: pixels (x + dx, y + dy), |dx|, |dy| <= window, inside the image; zmin, zmax over its surface pixels;
+ *        lo = zmin - (tol_abs + tol_rel * zmin);  hi = zmax + (tol_abs + tol_rel * zmax)
+ *     6  support  += 1 when the centre pixel is surface and lo <= d <= hi
+ *        conflict += 1 when every window pixel is surface and d < lo (the point floats in front of what u sees), or when carve is set
+ *                      and no window pixel is surface (u sees empty space there)
+ *        anything else -- behind the seen surface (occluded), a window that straddles a silhouette (undecided) -- is neither
+ * A row is kept when support >= min_support and conflicts <= max_conflicts.  support, conflicts [rows] uint8 (optional, each on its
+ * own) hold the votes saturated at 255, 0 on rows that are not live.
+ *
+ * ga_pc_voxel_thin: one kept row per occupied cell of a grid.
+ *     g_a = (p_a - origin_a) / voxel_size;  i_a = floor(g_a);  the row is DROPPED unless every g_a is finite and |i_a| <= 2^20 - 1
+ *     key = the three indices biased by 2^20, 21 bits each, x highest
+ *     GA_PC_VOXEL_CENTER: c_a = (F(i_a) + 0.5) * voxel_size + origin_a;  dl = p - c;  dist2 = (dl_x * dl_x + dl_y * dl_y) + dl_z * dl_z;
+ *                         rank = (bits(dist2) << 32) | r      (the bits of a non-negative float order as the float does)
+ *     GA_PC_VOXEL_FIRST:  rank = r
+ * The kept row of a cell is the one of smallest rank -- nearest the cell centre or first, ties to the lowest row: a measured point with
+ * its own colour and normal, never an average.  multiplicity [capacity] (optional) is the number of live rows in the kept row's cell, 0
+ * on padding; dropped [1] (optional) the number of dropped rows.
+ * MECHANISM: an open-addressing table in the workspace, table_slots slots (a power of two > rows; 0 = the smallest power of two >=
+ * 2 * rows) of a 64-bit key, a 64-bit rank and a 32-bit count.  Launches: clear (keys and ranks to all ones, counts and `dropped` to 0),
+ * insert (compare-and-swap on the key with linear probing, then min on the rank and add on the count; the slot of every row is kept in
+ * the workspace; with GA_PC_VOXEL_WAVE_MERGE a run of neighbouring lanes of a wave with one key is inserted once, with the run's
+ * smallest rank and its length: the same table, fewer atomics), then the compaction whose flag pass keeps row r when its slot's rank
+ * names r.  Every probe loop is bounded by
+ * table_slots iterations (never reached: table_slots > rows leaves an empty slot; a row that did reach it would be dropped and
+ * counted); inside the insert launch the table is touched through agent-scope integer atomics alone.  The hash is the implementation's
+ * own: no output depends on it or on the table's layout. */
+#define GA_PC_FILTER_THREADS 256
+#define GA_PC_FILTER_BAND_ROWS 1024
+#define GA_PC_FILTER_MAX_ROWS (1 << 30)
+#define GA_PC_VOXEL_FIRST 0
+#define GA_PC_VOXEL_CENTER 1
+#define GA_PC_VOXEL_MAX_INDEX 1048575  /* 2^20 - 1 */
+#define GA_PC_VOXEL_WAVE_MERGE 1       /* insert a run of neighbouring lanes with one key once (same outputs, other speed) */
+
+typedef struct GaFilterViewsArgs {
+    int32_t rows;             /* 1 .. GA_PC_FILTER_MAX_ROWS                                                */
+    int32_t capacity;         /* rows of the outputs, >= 1                                                 */
+    int32_t num_views;        /* V >= 1, V * H * W < 2^31                                                  */
+    int32_t height;           /* H >= 1                                                                    */
+    int32_t width;            /* W >= 1                                                                    */
+    int32_t depth_kind;       /* GA_PC_DEPTH_*                                                             */
+    int32_t window;           /* 0 or 1                                                                    */
+    int32_t min_support;      /* >= 0                                                                      */
+    int32_t max_conflicts;    /* >= 0                                                                      */
+    int32_t carve;            /* 0 or 1                                                                    */
+    float depth_min;          /* not NaN                                                                   */
+    float depth_max;          /* not NaN                                                                   */
+    float mask_threshold;     /* not NaN                                                                   */
+    float tol_abs;            /* >= 0, finite                                                              */
+    float tol_rel;            /* >= 0, finite                                                              */
+    int32_t reserved;         /* 0                                                                         */
+    const int32_t *in_count;  /* [1] or NULL                                                               */
+    const float *points;      /* [rows,3]                                                                  */
+    const float *colors;      /* [rows,3] or NULL                                                          */
+    const float *normals;     /* [rows,3] or NULL                                                          */
+    const int32_t *source;    /* [rows] or NULL                                                            */
+    const float *depth;       /* [V,H,W]                                                                   */
+    const float *mask;        /* [V,H,W] or NULL                                                           */
+    const float *cameras;     /* [V,GA_PC_CAMERA_FLOATS]                                                   */
+    float *out_points;        /* [capacity,3]                                                              */
+    float *out_colors;        /* [capacity,3]: given exactly when `colors` is                              */
+    float *out_normals;       /* [capacity,3]: given exactly when `normals` is                             */
+    int32_t *out_source;      /* [capacity]: given exactly when `source` is                                */
+    int32_t *kept_rows;       /* [capacity]                                                                */
+    int32_t *count;           /* [1]                                                                       */
+    int32_t *view_counts;     /* [V] or NULL; needs `source`                                               */
+    uint8_t *support;         /* [rows] or NULL                                                            */
+    uint8_t *conflicts;       /* [rows] or NULL                                                            */
+    void *workspace;          /* ga_pc_filter_views_workspace_bytes(rows) bytes, 16-byte aligned           */
+    size_t workspace_bytes;
+} GaFilterViewsArgs;
+
+typedef struct GaVoxelThinArgs {
+    int32_t rows;             /* 1 .. GA_PC_FILTER_MAX_ROWS                                                */
+    int32_t capacity;         /* rows of the outputs, >= 1                                                 */
+    int32_t keep;             /* GA_PC_VOXEL_*                                                             */
+    int32_t num_views;        /* entries of view_counts; >= 1 when it is given, else ignored               */
+    int32_t view_pixels;      /* H * W of the views `source` names; >= 1 when view_counts is given         */
+    int32_t flags;            /* 0 or GA_PC_VOXEL_WAVE_MERGE                                               */
+    float origin[3];          /* finite                                                                    */
+    float voxel_size;         /* positive, finite                                                          */
+    int64_t table_slots;      /* 0, or a power of two > rows and <= 2^31                                   */
+    const int32_t *in_count;  /* [1] or NULL                                                               */
+    const float *points;      /* [rows,3]                                                                  */
+    const float *colors;      /* [rows,3] or NULL                                                          */
+    const float *normals;     /* [rows,3] or NULL                                                          */
+    const int32_t *source;    /* [rows] or NULL                                                            */
+    float *out_points;        /* [capacity,3]                                                              */
+    float *out_colors;        /* [capacity,3]: given exactly when `colors` is                              */
+    float *out_normals;       /* [capacity,3]: given exactly when `normals` is                             */
+    int32_t *out_source;      /* [capacity]: given exactly when `source` is                                */
+    int32_t *kept_rows;       /* [capacity]                                                                */
+    int32_t *count;           /* [1]                                                                       */
+    int32_t *view_counts;     /* [num_views] or NULL; needs `source`                                       */
+    int32_t *multiplicity;    /* [capacity] or NULL                                                        */
+    int32_t *dropped;         /* [1] or NULL                                                               */
+    void *workspace;          /* ga_pc_voxel_thin_workspace_bytes(rows, table_slots) bytes, 16-byte aligned */
+    size_t workspace_bytes;
+} GaVoxelThinArgs;
+
+/* host: bytes of workspace each call needs, 0 for a shape it rejects */
+size_t ga_pc_filter_views_workspace_bytes(int32_t rows);
+size_t ga_pc_voxel_thin_workspace_bytes(int32_t rows, int64_t table_slots);
+/* GA_OK, GA_ERR_NULL_ARG (a required pointer, or an optional input without its output or the reverse, or view_counts without source),
+ * GA_ERR_BAD_SHAPE (rows, capacity, the views, table_slots), GA_ERR_BAD_FLAGS (a kind, window, carve, keep, reserved, a vote bound or a
+ * scalar out of its range), GA_ERR_WORKSPACE or GA_ERR_LAUNCH -- everything but the last before anything touches the device */
+int ga_pc_filter_views(const GaFilterViewsArgs *args, void *stream);
+int ga_pc_voxel_thin(const GaVoxelThinArgs *args, void *stream);
 
 #ifdef __cplusplus
 }
