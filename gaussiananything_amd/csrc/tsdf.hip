@@ -405,6 +405,7 @@ extern "C" size_t ga_tsdf_mesh_scratch_bytes(const GaTsdfVolume *volume)
 extern "C" int ga_tsdf_mesh_count(const GaTsdfVolume *volume, void *scratch, size_t scratch_bytes, int64_t *counts, void *stream_v)
 {
     using namespace ga;
+    if (!volume) return GA_ERR_NULL_ARG;
     VolP v;
     if (!make_vol(volume, v)) return GA_ERR_BAD_SHAPE;
     if (!scratch || !counts || !v.tsdf || !v.weight || !v.color || !v.allocated) return GA_ERR_NULL_ARG;
@@ -425,9 +426,10 @@ extern "C" int ga_tsdf_mesh_emit(const GaTsdfVolume *volume, void *scratch, size
                                  int64_t num_triangles, float *vertices, float *colors, int32_t *triangles, void *stream_v)
 {
     using namespace ga;
+    if (!volume) return GA_ERR_NULL_ARG;
     VolP v;
     if (!make_vol(volume, v)) return GA_ERR_BAD_SHAPE;
-    if (!scratch) return GA_ERR_NULL_ARG;
+    if (!scratch || !v.tsdf || !v.weight || !v.color || !v.allocated) return GA_ERR_NULL_ARG;   // (the volume ga_tsdf_mesh_count took)
     if (num_vertices < 0 || num_triangles < 0 || num_vertices > 0x7fffffffll / 3 || num_triangles > 0x7fffffffll / 3) return GA_ERR_BAD_SHAPE;
     if ((num_vertices > 0 && (!vertices || !colors)) || (num_triangles > 0 && !triangles)) return GA_ERR_NULL_ARG;
     MeshScratch ms;
@@ -437,7 +439,9 @@ extern "C" int ga_tsdf_mesh_emit(const GaTsdfVolume *volume, void *scratch, size
     hipStream_t s = reinterpret_cast<hipStream_t>(stream_v);
     (void)hipGetLastError();
     const unsigned units = (unsigned)(v.Ux * v.Uy * v.Uz);
-    if (num_vertices > 0) hipLaunchKernelGGL(mc_vertices_kernel, dim3(units), dim3(256), 0, s, v, m, vertices, colors, (int)num_vertices);
+    // the vertex pass also numbers the voxels (m.vid), which the triangle pass reads: it runs for triangles alone too, and with
+    // cap = 0 it writes no vertex
+    if (num_vertices > 0 || num_triangles > 0) hipLaunchKernelGGL(mc_vertices_kernel, dim3(units), dim3(256), 0, s, v, m, vertices, colors, (int)num_vertices);
     if (num_triangles > 0) hipLaunchKernelGGL(mc_triangles_kernel, dim3(units), dim3(256), 0, s, v, m, triangles, (int)num_triangles);
     return hipGetLastError() == hipSuccess ? GA_OK : GA_ERR_LAUNCH;
 }

@@ -72,7 +72,8 @@ int ga_tsdf_integrate(const GaTsdfVolume *volume, const GaTsdfFrame *frame, void
  *   ga_tsdf_mesh_emit  : after ga_tsdf_mesh_count on the same scratch; writes vertices [nv,3] (world coordinates), colors
  *                        [nv,3] in [0,1], triangles [nt,3] (vertex indices); order: units in lexicographic order, voxels in
  *                        storage order, edges x, y, z.  Pass the counts read back from the device; nothing is written
- *                        past them. */
+ *                        past them (a vertex iff its index is below the count, a cube's triangles iff all of them fit).
+ * Both take the same volume, with every array but `touched` present: a NULL volume or array is GA_ERR_NULL_ARG. */
 size_t ga_tsdf_mesh_scratch_bytes(const GaTsdfVolume *volume);
 int ga_tsdf_mesh_count(const GaTsdfVolume *volume, void *scratch, size_t scratch_bytes, int64_t *counts, void *stream);
 int ga_tsdf_mesh_emit(const GaTsdfVolume *volume, void *scratch, size_t scratch_bytes, int64_t num_vertices, int64_t num_triangles,

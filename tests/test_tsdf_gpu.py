@@ -12,24 +12,9 @@ import torch
 
 from gaussiananything_amd import mesh, synthetic
 from oracle import tsdf as otsdf
-from tests._tsdf_util import sphere_frames
+from tests._tsdf_util import check_mesh_invariants, fuse_both as _fuse_both, sphere_frames
 
 pytestmark = pytest.mark.gpu
-
-
-def _fuse_both(dev, frames, units, unit0, voxel, trunc, alpha_thres=0.08):
-    ovol = otsdf.Volume(units, unit0, voxel, trunc)
-    ul = voxel * 16
-    lo = [(u + 0.5) * ul for u in unit0]
-    hi = [(u0 + n - 0.5) * ul for u0, n in zip(unit0, units)]
-    hvol = mesh.TSDFVolume(voxel, trunc, lo, hi, device=dev)
-    assert hvol.units == list(units) and hvol.unit0 == list(unit0)
-    for f in frames:
-        touched = otsdf.integrate(ovol, f["rgb"], f["depth"], f["alpha"], alpha_thres, f["depth_trunc"], f["intr"], f["ext"])
-        hvol.integrate(torch.from_numpy(f["rgb"]), torch.from_numpy(f["depth"]), f["intr"], f["ext"], f["depth_trunc"],
-                       alpha=torch.from_numpy(f["alpha"]), alpha_thres=alpha_thres)
-        assert np.array_equal(hvol.touched.cpu().numpy().reshape(units).astype(bool), touched), "opened units differ"
-    return ovol, hvol
 
 
 def test_fusion_matches_the_oracle_voxel_by_voxel(gpu_device):
@@ -143,6 +128,10 @@ def test_export_mesh_from_rendered_views_end_to_end(gpu_device, tmp_path):
     v = np.array([[float(x) for x in l.split()[1:4]] for l in open(raw) if l.startswith("v ")])
     nt = sum(1 for l in open(raw) if l.startswith("f "))
     assert len(v) > 20000 and nt > 40000
+    # the one volume of real size (thousands of units, several trips of the unit scan) whose triangle indices are looked at
+    faces = np.array([[int(x) for x in l.split()[1:4]] for l in open(raw) if l.startswith("f ")], np.int64)
+    assert faces.shape == (nt, 3)
+    check_mesh_invariants(faces, len(v), base=1)
     rr = np.linalg.norm(v, axis=1)
     assert np.median(np.abs(rr - 0.3)) < 0.004 and np.percentile(np.abs(rr - 0.3), 99) < 0.03
     pv = np.array([[float(x) for x in l.split()[1:4]] for l in open(post) if l.startswith("v ")])
