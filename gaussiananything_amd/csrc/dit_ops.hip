@@ -2,10 +2,11 @@
 // elementwise torch ops:
 //   rmsnorm_modulate_kernel : RMSNorm (dit/norm.py:29-43) + t2i_modulate (dit_models_xformers.py:53-54) + bf16 cast
 //   small_linear_kernel     : the conditioning path's few-row Linear layers with SiLU (TimestepEmbedder :88-128,
-//                             pooled_vec_embedder dit_i23d.py:501-509, adaLN_modulation :209-214)
-//   timestep_freq_kernel    : sinusoidal features of t (TimestepEmbedder.timestep_embedding)
+//                             pooled_vec_embedder dit_i23d.py:501-509, adaLN_modulation :209-214), the sinusoidal features of t
+//                             (TimestepEmbedder.timestep_embedding) formed inside its first layer, and, behind the adaLN layer,
+//                             (scale_shift_table[None] + t0.reshape(B,6,-1)) for all blocks at once (:769-770, ModOut)
 //   layernorm_rows_kernel   : LayerNorm with affine of the pooled image vector (pooled_vec_embedder.0)
-//   mod_table_kernel        : (scale_shift_table[None] + t0.reshape(B,6,-1)) for all blocks at once (:769-770)
+//   shift_bias_kernel       : the shift rows of the folded modulated pre-norms through the qkv / fc1 weights
 //   embed_tokens_kernel     : x_embedder.fc1 + tanh-GELU (timm Mlp, K = 3 or 10) and the NeRF positional encoding +
 //                             xyz_projection of stage 2 (vit_triplane.py:187-229, utils/nerf_utils.py:16-66)
 //   final_layer_kernel      : T2IFinalLayer (dit_models_xformers.py:62-85): LayerNorm(no affine) + modulate + Linear
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(256) void small_linear_kernel(GaSmallLinearArgs a, 
     for (int b = 0; b < 16; ++b) acc[b] = 0.f;
     const uint16_t *w = a.W + (size_t)n * a.K;
     if (a.act_in == 2) {   // x = timesteps [B]; the input row is TimestepEmbedder.timestep_embedding(t) (K = 256), formed here
-        // exactly as timestep_freq_kernel forms it: [cos(t f_j) | sin(t f_j)], f_j = exp(-ln(10000) j / 128)
+        // as [cos(t f_j) | sin(t f_j)], f_j = exp(-ln(10000) j / 128)
         const int k = lane * 8;
         if (k < a.K) {
             const uint4 wr = *reinterpret_cast<const uint4 *>(w + k);
@@ -158,17 +159,6 @@ __global__ __launch_bounds__(256) void small_linear_kernel(GaSmallLinearArgs a, 
         }
 }
 
-__global__ void timestep_freq_kernel(const float *__restrict__ t, float *__restrict__ out, int B)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;  // B * 256
-    if (i >= B * 256) return;
-    const int b = i >> 8, j = i & 255, half = 128;
-    const int f = j < half ? j : j - half;
-    const float freq = expf(-9.210340371976184f * (float)f / (float)half);  // ln(10000)
-    const float arg = t[b] * freq;
-    out[i] = j < half ? cosf(arg) : sinf(arg);
-}
-
 __global__ __launch_bounds__(64) void layernorm_rows_kernel(const float *__restrict__ x, const float *__restrict__ w,
                                                             const float *__restrict__ bias, float *__restrict__ y,
                                                             int D, float eps)
@@ -182,25 +172,6 @@ __global__ __launch_bounds__(64) void layernorm_rows_kernel(const float *__restr
     for (int d = lane; d < D; d += 64) { const float c = xr[d] - mean; q += c * c; }
     const float rs = rsqrtf(wave_sum(q) / (float)D + eps);
     for (int d = lane; d < D; d += 64) y[(size_t)row * D + d] = (xr[d] - mean) * rs * w[d] + bias[d];
-}
-
-// mod[blk][b][j][d] = table_blk[j][d] + t0[b][j*D + d]      (j = shift_msa scale_msa gate_msa shift_mlp scale_mlp gate_mlp)
-struct ModTableArgs {
-    const float *tables[64];
-    const float *t0;
-    float *mod;
-    int depth, B, D;
-};
-
-__global__ void mod_table_kernel(ModTableArgs a)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t per_blk = (int64_t)a.B * 6 * a.D;
-    if (i >= per_blk * a.depth) return;
-    const int blk = (int)(i / per_blk);
-    const int64_t r = i - (int64_t)blk * per_blk;
-    const int b = (int)(r / (6 * a.D)), jd = (int)(r - (int64_t)b * 6 * a.D);
-    a.mod[i] = a.tables[blk][jd] + a.t0[(size_t)b * 6 * a.D + jd];
 }
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -437,3 +437,64 @@ def sin_cos(arg, P):
     """(cos ref, cos bound, sin ref, sin bound) of cosf / sinf(arg_hat), |arg_hat - arg| <= P, |arg| <= 1024: both 1-Lipschitz"""
     c, s = torch.cos(arg), torch.sin(arg)
     return c, P + COSF_REL * (c.abs() + P), s, P + SINF_REL * (s.abs() + P)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The denoiser's head and tail (dit_ops.hip: embed_tokens, final_layer, layernorm_rows, ctx_rmsnorm; tests/_headtail_cases.py).
+def fl_add_sparse(a, Pa, b, Pb=0.0):
+    """fl_add where an operand may be an exact zero: x + 0 is exact in fp32, so the rounding is counted only where both operands can be
+    non-zero.  (The planted weights make most addends of a sum exact zeros; the bound then counts the roundings that can happen.)"""
+    v = a + b
+    Pa = Pa if torch.is_tensor(Pa) else torch.full_like(v, Pa)
+    Pb = Pb if torch.is_tensor(Pb) else torch.full_like(v, Pb)
+    P = Pa + Pb
+    exact = ((a == 0) & (Pa == 0)) | ((b == 0) & (Pb == 0))
+    return v, torch.where(exact.expand_as(v), P, P + U * (v.abs() + P))
+
+
+def sparse_dot(x, dx, W, bias=None):
+    """fl(bias + sum_k x_k W_nk) of mirrored operands x (each may deviate by dx >= 0) against exact weights W [N, K], in any order:
+    products with an exact zero weight are exact zeros and adding them is exact, so a row of W with t non-zero entries costs t products
+    (exact for bf16 operands, counted as one rounding each for the fp32 ones) and t additions: gamma(2 t) on the absolute sum, as
+    `accumulation` counts it, with t in place of K.  Returns (ref, P)."""
+    t = (W != 0).sum(-1).to(x.dtype)
+    v = x @ W.T
+    E = dx @ W.abs().T
+    s = x.abs() @ W.abs().T + E
+    if bias is not None:
+        v, s, t = v + bias, s + bias.abs(), t + (bias != 0).to(x.dtype)
+    g = 2 * t * U / (1 - 2 * t * U)
+    return v, E + torch.where(t <= 1, torch.zeros_like(s), g * s)       # a single product of bf16 operands is exact
+
+
+def pivoted_layernorm_stats(x, Px, eps):
+    """final_layer_kernel: LayerNorm statistics in ONE reduction about the pivot p = x[0] of rows x_hat [..., D], |x_hat - x| <= Px:
+      v = fl(x_hat - p_hat)                     |v_hat - (x - p)| <= Dv = Px + Px[0] + u (|x - p| + Px + Px[0])     (element 0: exactly 0)
+      mean = fl(fl(sum v) / D)                  Dm = (1 + u) (sum Dv + gamma(D) sum (|v| + Dv)) / D + u |mean|
+      q = fl(sum fl(v^2)),  var = fl(fl(q / D) - fl(mean^2)), clamped at 0 (the true variance is >= 0: the clamp only helps)
+                                                dvar = dQ / D + d(mean^2) + gamma(3) (Q / D + mean^2 + their errors)
+      A = fl(var + eps), rs = rsqrtf(A)         as layernorm_stats
+      e = fl(v - mean)                          De = Dv + Dm + u (|e| + Dv + Dm)
+    Q / D and mean^2 are of the size of the spread about the pivot, not of the common offset: that is what the pivot buys, and what
+    the gamma(3) term charges an unpivoted kernel for.  Returns (e, De, r, rho)."""
+    D = x.shape[-1]
+    vv = x - x[..., :1]
+    Dv = Px + Px[..., :1] + U * (vv.abs() + Px + Px[..., :1])
+    Dv = torch.cat([torch.zeros_like(Dv[..., :1]), Dv[..., 1:]], -1)
+    av = vv.abs() + Dv
+    mu = vv.mean(-1, keepdim=True)
+    Dm = (1 + U) * (Dv.sum(-1, keepdim=True) + gamma(D) * av.sum(-1, keepdim=True)) / D + U * mu.abs()
+    e = vv - mu
+    De = Dv + Dm + U * (e.abs() + Dv + Dm)
+    m2 = vv.pow(2).mean(-1, keepdim=True)
+    dm2 = ((2 * vv.abs() * Dv + Dv * Dv).sum(-1, keepdim=True) + gamma(D + 1) * av.pow(2).sum(-1, keepdim=True)) / D
+    dmu2 = 2 * mu.abs() * Dm + Dm * Dm
+    var = m2 - mu * mu
+    dvar = dm2 + dmu2 + gamma(3) * (m2 + dm2 + mu * mu + dmu2)
+    A = var + eps
+    dA = dvar + U * (A + dvar)
+    xa = dA / A
+    assert bool((xa < 0.5).all()), "the statistics of a row are not determined to a factor of two: no bound"
+    r = torch.rsqrt(A)
+    rho = (1 + xa / (2 * (1 - xa))) * (1 + RSQRT_REL) - 1
+    return e, De, r, rho
