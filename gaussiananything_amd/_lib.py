@@ -177,6 +177,31 @@ class GaVoxelThinArgs(ctypes.Structure):
                [("workspace_bytes", ctypes.c_size_t)]
 
 
+class GaMeshSampleArgs(ctypes.Structure):
+    """include/ga_mesh.h: GaMeshSampleArgs"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("num_vertices", "num_faces", "num_samples", "reserved")] + [("seed", ctypes.c_uint64)] + \
+               [(n, ctypes.c_void_p) for n in ("seed_words", "vertices", "faces", "vertex_colors", "points", "face", "bary", "normals",
+                                               "colors", "workspace")] + [("workspace_bytes", ctypes.c_size_t)]
+
+
+class GaMeshSamplePlan(ctypes.Structure):
+    """include/ga_mesh.h: GaMeshSamplePlan"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("threads", "faces_per_group", "sums_per_trip", "num_groups")] + \
+               [("workspace_bytes", ctypes.c_size_t)]
+
+
+class GaMeshPointDistanceArgs(ctypes.Structure):
+    """include/ga_mesh.h: GaMeshPointDistanceArgs"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("num_points", "num_vertices", "num_faces", "reserved")] + \
+               [(n, ctypes.c_void_p) for n in ("points", "count", "vertices", "faces", "dist2", "face", "closest", "bary", "workspace")] + \
+               [("workspace_bytes", ctypes.c_size_t)]
+
+
+class GaMeshPointDistancePlan(ctypes.Structure):
+    """include/ga_mesh.h: GaMeshPointDistancePlan"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("threads", "tile", "tiles_per_chunk", "num_chunks")] + [("workspace_bytes", ctypes.c_size_t)]
+
+
 class GaPhotoLossArgs(ctypes.Structure):
     """include/ga_loss.h: GaPhotoLossArgs"""
     _fields_ = [("num_images", ctypes.c_int32), ("channels", ctypes.c_int32), ("height", ctypes.c_int32), ("width", ctypes.c_int32),
@@ -285,6 +310,7 @@ GA_PC_UNPROJECT_THREADS, GA_PC_UNPROJECT_TILE_PIXELS, GA_PC_UNPROJECT_MAX_WIDTH,
 GA_PC_CAMERA_FLOATS = 21
 GA_PC_FILTER_THREADS, GA_PC_FILTER_BAND_ROWS, GA_PC_FILTER_MAX_ROWS = 256, 1024, 1 << 30
 GA_PC_VOXEL_FIRST, GA_PC_VOXEL_CENTER, GA_PC_VOXEL_MAX_INDEX, GA_PC_VOXEL_WAVE_MERGE = 0, 1, (1 << 20) - 1, 1
+GA_MESH_THREADS, GA_MESH_PHILOX_STREAM, GA_MESH_MAX_FACES, GA_MESH_MAX_ROWS = 256, 0x4853454D, 1 << 27, 1 << 29
 
 EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspace_layout2", "ga_surfel_forward", "ga_surfel_postprocess",
            "ga_surfel_backward", "ga_surfel_backward_scratch_bytes", "ga_surfel_store_policy",
@@ -293,6 +319,7 @@ EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspa
            "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward", "ga_pc_normals", "ga_pc_normals_plan", "ga_pc_surfel_init",
            "ga_pc_unproject", "ga_pc_unproject_workspace_bytes",
            "ga_pc_filter_views", "ga_pc_filter_views_workspace_bytes", "ga_pc_voxel_thin", "ga_pc_voxel_thin_workspace_bytes",
+           "ga_mesh_sample_plan", "ga_mesh_sample", "ga_mesh_point_distance_plan", "ga_mesh_point_distance",
            "ga_photo_loss_plan", "ga_photo_loss_workspace_bytes", "ga_photo_loss_forward", "ga_photo_loss_backward",
            "ga_geo_loss_plan", "ga_geo_loss_workspace_bytes", "ga_geo_loss_forward", "ga_geo_loss_backward",
            "ga_fit_plan", "ga_fit_activate", "ga_fit_pack_grads", "ga_fit_adam", "ga_fit_advance", "ga_fit_select_views",
@@ -386,6 +413,14 @@ def lib():
         L.ga_pc_voxel_thin.argtypes = [ctypes.POINTER(GaVoxelThinArgs), ctypes.c_void_p]
         L.ga_pc_voxel_thin_workspace_bytes.restype = ctypes.c_size_t
         L.ga_pc_voxel_thin_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64]
+        L.ga_mesh_sample_plan.restype = ctypes.c_int
+        L.ga_mesh_sample_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GaMeshSamplePlan)]
+        L.ga_mesh_sample.restype = ctypes.c_int
+        L.ga_mesh_sample.argtypes = [ctypes.POINTER(GaMeshSampleArgs), ctypes.c_void_p]
+        L.ga_mesh_point_distance_plan.restype = ctypes.c_int
+        L.ga_mesh_point_distance_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GaMeshPointDistancePlan)]
+        L.ga_mesh_point_distance.restype = ctypes.c_int
+        L.ga_mesh_point_distance.argtypes = [ctypes.POINTER(GaMeshPointDistanceArgs), ctypes.c_void_p]
         L.ga_photo_loss_plan.restype = ctypes.c_int
         L.ga_photo_loss_plan.argtypes = [ctypes.c_int32] * 4 + [ctypes.POINTER(GaPhotoLossPlan)]
         L.ga_photo_loss_workspace_bytes.restype = ctypes.c_size_t

@@ -204,3 +204,19 @@ def from_point_cloud(stage2, decoder, cond, uc, points, cameras=None, cfg_scale=
     if stats is not None:
         stats.update(stage2=st2)
     return ret
+
+
+@torch.no_grad()
+def from_mesh(stage2, decoder, cond, uc, vertices, faces, num_surface_samples=16384, mesh_seed=0, **kw):
+    """``from_point_cloud`` for a user whose asset is a MESH: ``num_surface_samples`` area-weighted samples of its surface
+    (``mesh.sample_points_from_mesh`` with ``mesh_seed``) are the [S,N,3] cloud, every other keyword is ``from_point_cloud``'s.
+    ``vertices`` [V,3] and ``faces`` [F,3] for one conditioning; lists of S of each for S > 1 (one sampling call per mesh: batches of
+    meshes are not built).  The default of 16 384 samples keeps the farthest point sampling behind it on its register-resident path."""
+    from .mesh import sample_points_from_mesh
+    dev = next(stage2.parameters()).device
+    if isinstance(vertices, torch.Tensor):
+        vertices, faces = [vertices], [faces]
+    if len(vertices) != len(faces):
+        raise ValueError(f"{len(vertices)} vertex arrays for {len(faces)} face arrays")
+    cloud = torch.stack([sample_points_from_mesh(v.to(dev), f.to(dev), num_surface_samples, seed=mesh_seed) for v, f in zip(vertices, faces)])
+    return from_point_cloud(stage2, decoder, cond, uc, cloud, **kw)

@@ -376,6 +376,21 @@ def export_fps_points_from_depth(depth, c, path, K=4096, alpha_mask=None, depth_
     return pts
 
 
+def export_fps_points_from_mesh(vertices, faces, path, K=4096, num_samples=100000, seed=0):
+    """The ``fps-{K}.ply`` hand-off of a MESH: ``num_samples`` area-weighted samples of its surface (``mesh.sample_points_from_mesh``
+    with ``seed``), ``K`` farthest points of them starting from index 0, written as the vertex-only PLY ``export_fps_points`` writes.
+    ``vertices`` [V,3], ``faces`` [F,3]: arrays or tensors (moved to the GPU: sampling and FPS run there, no fallback).  Returns the
+    points, float32 [K, 3]."""
+    import torch
+    from .mesh import sample_points_from_mesh
+    from .pointcloud import sample_farthest_points
+    as_t = lambda a, dt: (a.detach() if hasattr(a, "detach") else torch.from_numpy(np.ascontiguousarray(a))).to("cuda", dt)  # noqa: E731
+    samples = sample_points_from_mesh(as_t(vertices, torch.float32), as_t(faces, torch.int32), num_samples, seed=seed)
+    pts = sample_farthest_points(samples[None], K=K)[0][0].cpu().numpy()
+    save_points_ply(path, pts)
+    return pts
+
+
 def save_glb(pointnp_px3, facenp_fx3, colornp_px3, fpath):
     """utils/mesh_util.py:127-136: vertices mirrored in x and z, vertex colours, triangles as given."""
     p = np.asarray(pointnp_px3, dtype=np.float64) @ np.array([[-1, 0, 0], [0, 1, 0], [0, 0, -1]])
@@ -391,6 +406,33 @@ def save_obj(pointnp_px3, facenp_fx3, colornp_px3, fpath):
     with open(fpath, "w") as fh:
         fh.write("".join("v %.8f %.8f %.8f %.5f %.5f %.5f\n" % (*a, *b) for a, b in zip(p.tolist(), c.tolist())))
         fh.write("".join("f %d %d %d\n" % tuple(t) for t in f.tolist()))
+
+
+def load_obj(path):
+    """Wavefront OBJ -> (vertices [V,3] float32, faces [F,3] int32, colors [V,3] float32 or None), on the host in numpy.  Reads
+    ``v x y z [r g b]`` (colours only when EVERY vertex carries them) and ``f`` lines in the ``i``, ``i/j``, ``i//k`` and ``i/j/k``
+    forms, 1-based, negative indices counting back from the vertices read so far; polygons are fan-triangulated around their first
+    corner.  Everything else (``vt``, ``vn``, groups, materials) is skipped.  Reads back what ``mesh.write_obj`` and ``save_obj``
+    write, as written: ``save_obj``'s z mirror and reversed winding are not undone."""
+    verts, cols, faces = [], [], []
+    with open(path, "r") as fh:
+        for line in fh:
+            t = line.split()
+            if not t:
+                continue
+            if t[0] == "v":
+                verts.append([float(x) for x in t[1:4]])
+                if len(t) >= 7:
+                    cols.append([float(x) for x in t[4:7]])
+            elif t[0] == "f":
+                idx = [int(c.split("/")[0]) for c in t[1:]]
+                idx = [i - 1 if i > 0 else len(verts) + i for i in idx]
+                if len(idx) < 3 or min(idx) < 0 or max(idx) >= len(verts):
+                    raise ValueError(f"{path}: face '{line.strip()}' does not name three vertices read before it")
+                faces += [[idx[0], idx[k], idx[k + 1]] for k in range(1, len(idx) - 1)]
+    v = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+    c = np.asarray(cols, dtype=np.float32).reshape(-1, 3) if verts and len(cols) == len(verts) else None
+    return v, np.asarray(faces, dtype=np.int32).reshape(-1, 3), c
 
 
 # ---- surfel Gaussians as a 2DGS-style PLY (nsr/gs_surfel.py:206-265) -------------------------------------------------------

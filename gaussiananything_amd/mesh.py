@@ -7,7 +7,12 @@ Mirrors the reference's mesh export of a generated object, function by function:
 with Open3D's ScalableTSDFVolume (CPU, third party) replaced by ``TSDFVolume`` (HIP kernels, csrc/tsdf.hip; dense over the
 bounding cube, which 288 GB of HBM afford).  Fusion, marching cubes and the connected-component filter of ``post_process_mesh`` run on the GPU; the OBJ
 writer is a host function of the library.  There is no CPU
-fallback: without the HIP library the calls raise."""
+fallback: without the HIP library the calls raise.
+
+Meshes IN, at the end of the file (include/ga_mesh.h, csrc/mesh_ops.hip): ``sample_points_from_mesh`` (area-weighted
+surface samples), ``point_mesh_distance`` (distance to the surface, brute force) and ``mesh_cloud_distance`` (our own, unpinned
+accuracy / completeness / F-score between a mesh and a cloud)."""
+import collections
 import ctypes
 import math
 import os
@@ -17,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .pointcloud import _stream
 
 UNIT = 16
 
@@ -250,3 +256,150 @@ def export_mesh_from_2dgs(all_rgbs, all_depths, all_alphas, cam_pathes, mesh_out
     post_path = mesh_output_path.replace("_raw.obj", ".obj")
     write_obj(post_path, pv, pc, pt)
     return post_path
+
+
+# ---- meshes in: surface sampling and the point-to-surface distance (include/ga_mesh.h, csrc/mesh_ops.hip) --------------------------
+# One mesh per call: batches of meshes are not built, a caller loops.
+
+def _mesh(vertices, faces):
+    """fp32 [V,3] and int32 [F,3] contiguous device copies of a mesh; GPU only"""
+    if not isinstance(vertices, torch.Tensor) or not isinstance(faces, torch.Tensor):
+        raise ValueError("vertices and faces are tensors")
+    if vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.shape[0] < 1 or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError("a mesh is vertices [V, 3] and faces [F, 3] with V, F >= 1 (one mesh per call)")
+    if vertices.device.type != "cuda" or faces.device != vertices.device:
+        raise RuntimeError("the mesh must be on the GPU (no CPU fallback)")
+    return vertices.detach().to(torch.float32).contiguous(), faces.detach().to(torch.int32).contiguous()
+
+
+def mesh_sample_plan(num_faces: int, num_samples: int = 1) -> dict:
+    """What ``ga_mesh_sample`` does for a mesh of ``num_faces``: {'threads', 'faces_per_group', 'sums_per_trip', 'num_groups',
+    'workspace_bytes'}."""
+    pl = _lib.GaMeshSamplePlan()
+    _lib.check(_lib.lib().ga_mesh_sample_plan(int(num_faces), int(num_samples), ctypes.byref(pl)), "ga_mesh_sample_plan")
+    return {n: int(getattr(pl, n)) for n, _ in pl._fields_}
+
+
+def point_mesh_distance_plan(num_points: int, num_faces: int) -> dict:
+    """What ``ga_mesh_point_distance`` does: {'threads', 'tile', 'tiles_per_chunk', 'num_chunks', 'workspace_bytes'}."""
+    pl = _lib.GaMeshPointDistancePlan()
+    _lib.check(_lib.lib().ga_mesh_point_distance_plan(int(num_points), int(num_faces), ctypes.byref(pl)), "ga_mesh_point_distance_plan")
+    return {n: int(getattr(pl, n)) for n, _ in pl._fields_}
+
+
+@torch.no_grad()
+def sample_points_from_mesh(vertices, faces, num_samples: int = 10000, *, colors=None, seed=0, return_normals: bool = False,
+                            return_faces: bool = False):
+    """Area-weighted samples of a triangle mesh's surface, what ``pytorch3d.ops.sample_points_from_meshes`` gives for one mesh (its
+    barycentric formula; the random stream and the face search are this project's, parity unpinned): -> points [S,3], or a tuple
+    (points[, normals][, colors][, (face [S] int64, bary [S,3])]) in that order for what is asked.  ``colors`` [V,3]: per-vertex
+    colours, interpolated barycentrically.  ``seed``: an int, or a device tensor of two 32-bit words (int32 or uint32: low, high) that
+    the kernel reads when it runs -- a captured graph draws fresh samples after the tensor is overwritten.  Faces with an index out of
+    range or of zero or non-finite area are never drawn; a mesh without any other face yields face -1 and zero rows.  Three launches
+    on the current stream, no host read; the tensors stay on the mesh's device."""
+    v, f = _mesh(vertices, faces)
+    S = int(num_samples)
+    if S < 1:
+        raise ValueError("num_samples must be at least 1")
+    dev = v.device
+    vc = None
+    if colors is not None:
+        if colors.shape != v.shape or colors.device != dev:
+            raise ValueError("colors is a [V, 3] tensor on the mesh's device")
+        vc = colors.detach().to(torch.float32).contiguous()
+    words, host_seed = None, 0
+    if isinstance(seed, torch.Tensor):
+        if seed.device != dev or seed.numel() != 2 or seed.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not seed.is_contiguous():
+            raise ValueError("a device seed is a contiguous tensor of two 32-bit words on the mesh's device")
+        words = seed
+    else:
+        host_seed = int(seed) & ((1 << 64) - 1)
+    L = _lib.lib()
+    pl = _lib.GaMeshSamplePlan()
+    _lib.check(L.ga_mesh_sample_plan(f.shape[0], S, ctypes.byref(pl)), "ga_mesh_sample_plan")
+    ws = torch.empty(pl.workspace_bytes, dtype=torch.uint8, device=dev)
+    points = torch.empty(S, 3, dtype=torch.float32, device=dev)
+    face = torch.empty(S, dtype=torch.int32, device=dev)
+    bary = torch.empty(S, 3, dtype=torch.float32, device=dev)
+    normals = torch.empty(S, 3, dtype=torch.float32, device=dev) if return_normals else None
+    out_colors = torch.empty(S, 3, dtype=torch.float32, device=dev) if vc is not None else None
+    ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+    args = _lib.GaMeshSampleArgs(v.shape[0], f.shape[0], S, 0, host_seed, ptr(words), v.data_ptr(), f.data_ptr(), ptr(vc),
+                                 points.data_ptr(), face.data_ptr(), bary.data_ptr(), ptr(normals), ptr(out_colors), ws.data_ptr(),
+                                 pl.workspace_bytes)
+    with torch.cuda.device(dev):
+        _lib.check(L.ga_mesh_sample(ctypes.byref(args), _stream(dev)), "ga_mesh_sample")
+    ret = [points] + ([normals] if return_normals else []) + ([out_colors] if vc is not None else []) + \
+          ([(face.long(), bary)] if return_faces else [])
+    return ret[0] if len(ret) == 1 else tuple(ret)
+
+
+PointMeshDistance = collections.namedtuple("PointMeshDistance", "dist2 face closest bary")
+PointMeshDistance.__doc__ = """``point_mesh_distance``'s result: dist2 [N] squared distance to the surface, face [N] int64 (the lowest
+index among equally near faces; -1 on padding rows and without a valid triangle), closest [N,3] the nearest surface point, bary [N,3]
+its barycentric weights on that face"""
+
+
+def point_mesh_distance(points, vertices, faces, *, differentiable: bool = False):
+    """Squared distance of every point to the SURFACE of a triangle mesh (not to its vertices), brute force over all faces on the
+    device: -> ``PointMeshDistance``.  ``points``: a [N,3] tensor, or an untrimmed ``UnprojectedCloud`` / ``FilteredCloud`` (anything with
+    ``points`` [N,3] and a device ``count``): rows past the count get distance 0 and face -1, the padding of ``nearest_points``.
+    Degenerate and out-of-range faces are skipped; a row with no valid face gets +inf and -1.
+
+    ``differentiable=True``: ``dist2`` is computed again in torch as ``|p - sum_k bary_k * vertices[faces[face], k]|^2`` with ``bary``
+    and ``face`` detached.  The nearest point minimises the distance over the triangle, so by the envelope argument the derivative of
+    the minimum is the derivative of this expression at the fixed minimiser: it is the gradient with respect to both ``points`` and
+    ``vertices`` wherever the nearest face is unique.  No backward kernel is needed, and none is built."""
+    count = None
+    if not isinstance(points, torch.Tensor):
+        points, count = points.points, points.count
+    v, f = _mesh(vertices, faces)
+    if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1 or points.device != v.device:
+        raise ValueError("points is a [N, 3] tensor with N >= 1 on the mesh's device")
+    p = points.detach().to(torch.float32).contiguous()
+    dev, N = v.device, p.shape[0]
+    if count is not None:
+        count = count.detach().to(torch.int32).reshape(-1)[:1].contiguous()
+    L = _lib.lib()
+    pl = _lib.GaMeshPointDistancePlan()
+    _lib.check(L.ga_mesh_point_distance_plan(N, f.shape[0], ctypes.byref(pl)), "ga_mesh_point_distance_plan")
+    with torch.no_grad():
+        ws = torch.empty(pl.workspace_bytes, dtype=torch.uint8, device=dev)
+        dist2 = torch.empty(N, dtype=torch.float32, device=dev)
+        face = torch.empty(N, dtype=torch.int32, device=dev)
+        closest = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        bary = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        args = _lib.GaMeshPointDistanceArgs(N, v.shape[0], f.shape[0], 0, p.data_ptr(), count.data_ptr() if count is not None else None,
+                                            v.data_ptr(), f.data_ptr(), dist2.data_ptr(), face.data_ptr(), closest.data_ptr(),
+                                            bary.data_ptr(), ws.data_ptr(), pl.workspace_bytes)
+        with torch.cuda.device(dev):
+            _lib.check(L.ga_mesh_point_distance(ctypes.byref(args), _stream(dev)), "ga_mesh_point_distance")
+        face = face.long()
+    if differentiable:
+        hit = face >= 0
+        corners = vertices[faces.long()[face.clamp(min=0)]]                      # [N,3,3], differentiable in `vertices`
+        nearest = (bary.unsqueeze(-1) * corners.to(torch.float32)).sum(1)
+        d = ((points.to(torch.float32) - nearest) ** 2).sum(-1)
+        dist2 = torch.where(hit, d, dist2)                                       # padding and faceless rows keep 0 / +inf, no gradient
+    return PointMeshDistance(dist2, face, closest, bary)
+
+
+@torch.no_grad()
+def mesh_cloud_distance(vertices, faces, points, *, num_samples: int = 100000, threshold: Optional[float] = None, seed=0):
+    """How far a mesh lies from a cloud -- this project's OWN definition (no reference code for it runs here: UNPINNED):
+        accuracy      mean distance from ``num_samples`` surface samples of the mesh to their nearest cloud point (``nearest_points``)
+        completeness  mean distance from the cloud's points to the mesh surface (``point_mesh_distance``)
+    and, with ``threshold`` (a distance), precision = the share of samples within it, recall = the share of cloud points within it and
+    fscore = their harmonic mean (0 when both are 0).  ``points`` [N,3].  Distances, not squared.  -> dict of 0-dim device tensors;
+    nothing is read back."""
+    from .pointcloud import nearest_points
+    samples = sample_points_from_mesh(vertices, faces, num_samples, seed=seed)
+    cloud = points.detach().to(torch.float32).contiguous()
+    to_cloud = nearest_points(samples[None], cloud[None])[0][0].sqrt()
+    to_mesh = point_mesh_distance(cloud, vertices, faces).dist2.sqrt()
+    out = {"accuracy": to_cloud.mean(), "completeness": to_mesh.mean()}
+    if threshold is not None:
+        precision, recall = (to_cloud <= threshold).float().mean(), (to_mesh <= threshold).float().mean()
+        both = precision + recall
+        out.update(precision=precision, recall=recall, fscore=torch.where(both > 0, 2 * precision * recall / both.clamp(min=1e-30), both))
+    return out
