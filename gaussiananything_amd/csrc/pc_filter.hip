@@ -4,7 +4,7 @@
 // Built with -ffp-contract=off: every operation is rounded on its own, division, square root and floor are exact or correctly rounded,
 // so the kernels are a function of their inputs alone and tests/_pc_filter_ref.py restates them in numpy float32 bit for bit.
 //
-// Both calls end in the three-launch ordered compaction of csrc/pc_unproject.hip, here over bands of kBandRows consecutive ROWS:
+// Both calls end in the three-launch ordered compaction built from csrc/compact.h, here over bands of kBandRows consecutive ROWS:
 //   flag     one flag byte per row and the band's count (filter_vote_kernel for the filter, voxel_flag_kernel for the thinning)
 //   scan     ONE workgroup, kThreads band counts a trip with a register carry: exclusive offsets, count; view_counts zeroed
 //   scatter  ballot + popcount ranks, copies the kept rows, adds them to view_counts; further workgroups write the padding
@@ -16,14 +16,16 @@
 #include <stdint.h>
 
 #include "../../include/ga_pointcloud.h"
+#include "compact.h"
 
 namespace {
+
+using namespace gacompact;
 
 constexpr int kThreads = GA_PC_FILTER_THREADS;
 constexpr int kWaves = kThreads / 64;
 constexpr int kBandRows = GA_PC_FILTER_BAND_ROWS;
 constexpr int kTrips = kBandRows / kThreads;
-constexpr int kPadRows = 1024;   // padding rows per workgroup of the scatter launch
 constexpr int kCam = GA_PC_CAMERA_FLOATS;
 constexpr unsigned long long kEmpty = ~0ull;   // no key (63 bits) and no rank of a row equals it
 
@@ -54,20 +56,6 @@ __device__ __forceinline__ int live_rows(const Compact &c) {
         n = given < 0 ? 0 : (given < n ? given : n);
     }
     return n;
-}
-
-// the end of a flag pass: the band's count from every lane's own
-__device__ __forceinline__ void band_total(const Compact &c, int mine, int *wave_sum) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_down(mine, d, 64);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) total += wave_sum[w];
-        c.bands[blockIdx.x] = total;
-    }
 }
 
 // ---- the filter's flag pass: one lane per row, every view votes ---------------------------------------------------------------------------
@@ -145,7 +133,8 @@ __global__ __launch_bounds__(kThreads) void filter_vote_kernel(GaFilterViewsArgs
         c.flags[r] = keep ? 1 : 0;
         mine += keep ? 1 : 0;
     }
-    band_total(c, mine, wave_sum);
+    const int total = block_sum<kWaves>(mine, wave_sum);
+    if (threadIdx.x == 0) c.bands[blockIdx.x] = total;   // the band's count
 }
 
 // ---- the thinning's table ----------------------------------------------------------------------------------------------------------------
@@ -257,47 +246,15 @@ __global__ __launch_bounds__(kThreads) void voxel_flag_kernel(Table t, Compact c
         c.flags[r] = keep ? 1 : 0;
         mine += keep ? 1 : 0;
     }
-    band_total(c, mine, wave_sum);
+    const int total = block_sum<kWaves>(mine, wave_sum);
+    if (threadIdx.x == 0) c.bands[blockIdx.x] = total;   // the band's count
 }
 
 // ---- scan and scatter ----------------------------------------------------------------------------------------------------------------------
-// inclusive scan over the 64 lanes of a wave
-__device__ __forceinline__ int wave_scan(int x) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-
 __global__ __launch_bounds__(kThreads) void compact_scan_kernel(Compact c) {
     __shared__ int lds[kWaves];
-    int32_t *sums = c.bands;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int carry = 0;   // at most rows <= 2^30
-    for (int start = 0; start < c.num_bands; start += kThreads) {   // (every lane takes every trip: the barriers are uniform)
-        const int b = start + (int)threadIdx.x;
-        const int n = b < c.num_bands ? sums[b] : 0;
-        const int incl = wave_scan(n);
-        if (lane == 63) lds[wave] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const int s = lds[w];
-            before += w < wave ? s : 0;
-            all += s;
-        }
-        __syncthreads();
-        if (b < c.num_bands) sums[b] = carry + before + (incl - n);   // the band's exclusive offset, in place of its count
-        carry += all;
-    }
-    if (threadIdx.x == 0) {
-        sums[c.num_bands] = carry;
-        c.count[0] = carry;
-    }
+    const int total = scan_counts_in_place<kThreads>(c.bands, c.num_bands, lds);   // at most rows <= 2^30
+    if (threadIdx.x == 0) c.count[0] = total;
     if (c.view_counts)
         for (int v = threadIdx.x; v < c.num_views; v += kThreads) c.view_counts[v] = 0;   // the scatter launch adds to them
 }
@@ -306,11 +263,8 @@ __global__ __launch_bounds__(kThreads) void compact_scatter_kernel(Compact c) {
     __shared__ int wave_sum[kWaves];
     const int64_t cap = c.capacity;
     if ((int)blockIdx.x >= c.num_bands) {   // padding: rows min(count, capacity) .. capacity - 1
-        const int64_t total = c.bands[c.num_bands];
-        const int64_t first = (int64_t)((int)blockIdx.x - c.num_bands) * kPadRows;
-        int64_t lo = total < cap ? total : cap;
-        lo = lo > first ? lo : first;
-        const int64_t hi = first + kPadRows < cap ? first + kPadRows : cap;
+        int64_t lo, hi;
+        pad_range((int)blockIdx.x - c.num_bands, c.bands[c.num_bands], cap, lo, hi);
         for (int64_t r = lo + threadIdx.x; r < hi; r += kThreads) {
             c.o_points[3 * r] = 0.f; c.o_points[3 * r + 1] = 0.f; c.o_points[3 * r + 2] = 0.f;
             if (c.o_colors) { c.o_colors[3 * r] = 0.f; c.o_colors[3 * r + 1] = 0.f; c.o_colors[3 * r + 2] = 0.f; }
@@ -330,18 +284,8 @@ __global__ __launch_bounds__(kThreads) void compact_scatter_kernel(Compact c) {
     for (int trip = 0; trip < kTrips && row0 < row_end && (row0 < cap || c.view_counts); ++trip) {
         const int64_t in = (int64_t)blockIdx.x * kBandRows + trip * kThreads + (int)threadIdx.x;
         const bool ok = in < c.rows && c.flags[in] != 0;
-        const unsigned long long vote = __ballot(ok);
-        if (lane == 0) wave_sum[wave] = __popcll(vote);
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const int s = wave_sum[w];
-            before += w < wave ? s : 0;
-            all += s;
-        }
-        __syncthreads();
-        const int64_t r = row0 + before + __popcll(vote & ((1ull << lane) - 1ull));
+        int all;
+        const int64_t r = row0 + block_ballot_rank<kWaves>(ok, wave_sum, all);
         int src = -1;
         if (ok && c.source) src = c.source[in];
         if (ok && r < cap) {
@@ -421,9 +365,8 @@ unsigned long long slots_of(int64_t rows, int64_t table_slots) {
 }
 
 void launch_compaction(const Compact &c, hipStream_t st) {
-    const unsigned pad_blocks = (unsigned)(((int64_t)c.capacity + kPadRows - 1) / kPadRows);
     hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kThreads), 0, st, c);
-    hipLaunchKernelGGL(compact_scatter_kernel, dim3((unsigned)c.num_bands + pad_blocks), dim3(kThreads), 0, st, c);
+    hipLaunchKernelGGL(compact_scatter_kernel, dim3((unsigned)c.num_bands + pad_blocks(c.capacity)), dim3(kThreads), 0, st, c);
 }
 
 }  // namespace

@@ -3,8 +3,8 @@
 // Built with -ffp-contract=off: every operation is rounded on its own, division and square root are hipcc's correctly rounded defaults,
 // so the kernels are a function of their inputs alone and tests/_unproject_ref.py restates them in numpy float32 bit for bit.
 //
-// An ordered stream compaction whose output size is data dependent, as the three launches of csrc/surfel_densify.hip -- no workgroup
-// waits for another one, there is no look-back, no spinning, no atomics:
+// An ordered stream compaction whose output size is data dependent, three launches built from csrc/compact.h -- no workgroup waits for
+// another one, there is no look-back, no spinning, no atomics:
 //   1 flag     a workgroup owns a band of full rows of one view (band order = source order).  With erode > 0 the thresholded mask of the
 //              band and an erode-wide halo is staged in LDS as bytes (outside the image: foreground) and a pixel is foreground when the
 //              whole diamond |dx| + |dy| <= erode is: e iterations of the 3 x 3 cross.  kThreads consecutive pixels per trip, coalesced;
@@ -19,13 +19,15 @@
 #include <stdint.h>
 
 #include "../../include/ga_pointcloud.h"
+#include "compact.h"
 
 namespace {
+
+using namespace gacompact;
 
 constexpr int kThreads = GA_PC_UNPROJECT_THREADS;
 constexpr int kWaves = kThreads / 64;
 constexpr int kTilePixels = GA_PC_UNPROJECT_TILE_PIXELS;
-constexpr int kPadRows = 1024;   // padding rows per workgroup of the scatter launch
 constexpr int kCam = GA_PC_CAMERA_FLOATS;
 
 struct Shape {
@@ -123,55 +125,15 @@ __global__ __launch_bounds__(kThreads) void unproject_flag_kernel(GaUnprojectArg
         flags[at] = ok ? 1 : 0;
         mine += ok ? 1 : 0;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) mine += __shfl_down(mine, d, 64);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int total = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) total += wave_sum[w];
-        reinterpret_cast<int32_t *>(a.workspace)[blockIdx.x] = total;
-    }
-}
-
-// inclusive scan over the 64 lanes of a wave
-__device__ __forceinline__ int wave_scan(int x) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
+    const int total = block_sum<kWaves>(mine, wave_sum);
+    if (threadIdx.x == 0) reinterpret_cast<int32_t *>(a.workspace)[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kThreads) void unproject_scan_kernel(GaUnprojectArgs a, Shape s) {
     __shared__ int lds[kWaves];
     int32_t *sums = reinterpret_cast<int32_t *>(a.workspace);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int carry = 0;   // at most V * H * W < 2^31
-    for (int start = 0; start < s.num_blocks; start += kThreads) {   // (every lane takes every trip: the barriers are uniform)
-        const int b = start + (int)threadIdx.x;
-        const int c = b < s.num_blocks ? sums[b] : 0;
-        const int incl = wave_scan(c);
-        if (lane == 63) lds[wave] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const int t = lds[w];
-            before += w < wave ? t : 0;
-            all += t;
-        }
-        __syncthreads();
-        if (b < s.num_blocks) sums[b] = carry + before + (incl - c);   // the band's exclusive offset, in place of its count
-        carry += all;
-    }
-    if (threadIdx.x == 0) {
-        sums[s.num_blocks] = carry;
-        a.count[0] = carry;
-    }
+    const int total = scan_counts_in_place<kThreads>(sums, s.num_blocks, lds);   // at most V * H * W < 2^31
+    if (threadIdx.x == 0) a.count[0] = total;
     __syncthreads();   // the offsets this workgroup wrote are read back below
     for (int v = threadIdx.x; v < a.num_views; v += kThreads)
         a.view_counts[v] = sums[(v + 1) * s.blocks_per_view] - sums[v * s.blocks_per_view];
@@ -182,11 +144,8 @@ __global__ __launch_bounds__(kThreads) void unproject_scatter_kernel(GaUnproject
     const int32_t *offs = reinterpret_cast<const int32_t *>(a.workspace);
     const int64_t cap = a.capacity;
     if ((int)blockIdx.x >= s.num_blocks) {   // padding: rows min(count, capacity) .. capacity - 1
-        const int64_t total = offs[s.num_blocks];
-        const int64_t first = (int64_t)((int)blockIdx.x - s.num_blocks) * kPadRows;
-        int64_t lo = total < cap ? total : cap;
-        lo = lo > first ? lo : first;
-        const int64_t hi = first + kPadRows < cap ? first + kPadRows : cap;
+        int64_t lo, hi;
+        pad_range((int)blockIdx.x - s.num_blocks, offs[s.num_blocks], cap, lo, hi);
         for (int64_t r = lo + threadIdx.x; r < hi; r += kThreads) {
             a.points[3 * r] = 0.f; a.points[3 * r + 1] = 0.f; a.points[3 * r + 2] = 0.f;
             if (a.colors) { a.colors[3 * r] = 0.f; a.colors[3 * r + 1] = 0.f; a.colors[3 * r + 2] = 0.f; }
@@ -203,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void unproject_scatter_kernel(GaUnproject
     const float *cam = a.cameras + (int64_t)v * kCam;
     const float inv_w = 1.f / (float)W, half_w = 0.5f / (float)W, inv_h = 1.f / (float)H, half_h = 0.5f / (float)H;
     const unsigned char *flags = reinterpret_cast<const unsigned char *>(a.workspace) + flags_offset(s);
-    const int pixels = rows * W, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pixels = rows * W;
     int64_t row0 = offs[blockIdx.x];
     const int64_t row_end = offs[blockIdx.x + 1];
     for (int start = 0; start < pixels && row0 < row_end && row0 < cap; start += kThreads) {   // (uniform: the barriers are safe)
@@ -214,18 +173,8 @@ __global__ __launch_bounds__(kThreads) void unproject_scatter_kernel(GaUnproject
             ry = p / W; x = p - ry * W;
             ok = flags[view0 + (int64_t)(y0 + ry) * W + x] != 0;
         }
-        const unsigned long long vote = __ballot(ok);
-        if (lane == 0) wave_sum[wave] = __popcll(vote);
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const int t = wave_sum[w];
-            before += w < wave ? t : 0;
-            all += t;
-        }
-        __syncthreads();
-        const int64_t r = row0 + before + __popcll(vote & ((1ull << lane) - 1ull));
+        int all;
+        const int64_t r = row0 + block_ballot_rank<kWaves>(ok, wave_sum, all);
         if (ok && r < cap) {
             const int y = y0 + ry;
             const int64_t at = view0 + (int64_t)y * W + x;
@@ -286,11 +235,10 @@ extern "C" int ga_pc_unproject(const GaUnprojectArgs *args, void *stream_v) {
     const int halo = a.mask ? a.erode : 0;
     // at most (1024 + 8) rows of 1 + 8 bytes, or 9 rows of 4096 + 8: under 37 KB
     const size_t lds = halo > 0 ? (size_t)(s.rows_per_block + 2 * halo) * (size_t)(a.width + 2 * halo) : 0;
-    const unsigned pad_blocks = (unsigned)(((int64_t)a.capacity + kPadRows - 1) / kPadRows);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream_v);
     (void)hipGetLastError();
     hipLaunchKernelGGL(unproject_flag_kernel, dim3(s.num_blocks), dim3(kThreads), lds, st, a, s, halo);
     hipLaunchKernelGGL(unproject_scan_kernel, dim3(1), dim3(kThreads), 0, st, a, s);
-    hipLaunchKernelGGL(unproject_scatter_kernel, dim3((unsigned)s.num_blocks + pad_blocks), dim3(kThreads), 0, st, a, s);
+    hipLaunchKernelGGL(unproject_scatter_kernel, dim3((unsigned)s.num_blocks + pad_blocks(a.capacity)), dim3(kThreads), 0, st, a, s);
     return hipGetLastError() == hipSuccess ? GA_OK : GA_ERR_LAUNCH;
 }

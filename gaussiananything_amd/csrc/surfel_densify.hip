@@ -5,8 +5,8 @@
 // restatement the tests hold them to (tests/_densify_ref.py); the normals of a split come from the device library's log / sin / cos and
 // are handed out (noise_out) instead of being pinned.
 //   accumulate   one lane per surfel: V radii and V view rows read, three words updated; part of the captured iteration
-//   densify      a stream compaction whose output size is data dependent, as three launches ordered by the stream -- no workgroup
-//                waits for another one, there is no look-back, no spinning, no device-wide barrier:
+//   densify      a stream compaction whose output size is data dependent, as three launches ordered by the stream, built from
+//                csrc/compact.h -- no workgroup waits for another one, there is no look-back, no spinning, no device-wide barrier:
 //                  1 count     one lane per kRows consecutive surfels: classify, reduce the block's emitted rows and tallies
 //                  2 scan      ONE workgroup walks the block sums kThreads at a time (carry in a register), writes each block's
 //                              exclusive offset in place and the totals to out_counts
@@ -19,9 +19,12 @@
 #include <stdint.h>
 
 #include "../../include/ga_densify.h"
+#include "compact.h"
 #include "philox.h"
 
 namespace ga {
+
+using namespace gacompact;
 
 constexpr int kThreads = GA_DENSIFY_THREADS;
 constexpr int kRows = GA_DENSIFY_ROWS_PER_LANE;
@@ -75,38 +78,6 @@ __device__ __forceinline__ int densify_classify(const GaDensifyArgs &a, int i)
 
 __device__ __forceinline__ int emitted(int code) { return code == kPruned ? 0 : (code == kKept ? 1 : 2); }
 
-// inclusive scan over the 64 lanes of a wave
-__device__ __forceinline__ int wave_scan(int x)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-    }
-    return x;
-}
-
-// inclusive scan over the workgroup; `total` is the workgroup's sum.  `lds` holds kWaves words; two barriers, the second one leaves
-// `lds` free for the next call
-__device__ __forceinline__ int block_scan(int x, int *lds, int &total)
-{
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int incl = wave_scan(x);
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const int s = lds[w];
-        before += w < wave ? s : 0;
-        all += s;
-    }
-    __syncthreads();
-    total = all;
-    return incl + before;
-}
-
 __global__ __launch_bounds__(kThreads) void densify_count_kernel(GaDensifyArgs a)
 {
     __shared__ int lds[4][kWaves];
@@ -151,27 +122,17 @@ __global__ __launch_bounds__(kThreads) void densify_scan_kernel(GaDensifyArgs a,
         if (b < num_blocks) s = sums[b];
         t[0] += s.y; t[1] += s.z; t[2] += s.w;
         int total;
-        const int incl = block_scan(s.x, lds, total);
+        const int incl = block_inclusive_scan<kWaves>(s.x, lds, total);
         if (b < num_blocks) {
             s.x = (int)(carry + (incl - s.x));                         // the block's exclusive offset, in place of its sum
             sums[b] = s;
         }
         carry += total;
     }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    long long s[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) t[k] += __shfl_down(t[k], d, 64);
-        if (lane == 0) tally[k][wave] = t[k];
-    }
-    __syncthreads();
+    for (int k = 0; k < 3; ++k) s[k] = block_sum<kWaves>(t[k], tally[k]);
     if (threadIdx.x == 0) {
-        long long s[3] = {0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) s[k] += tally[k][w];
         const long long n = a.num_points;
         a.out_counts[0] = carry;
         a.out_counts[1] = n - s[0] - s[1] - s[2];
@@ -226,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void densify_scatter_kernel(GaDensifyArgs
         mine += emitted(code[j]);
     }
     int total;
-    int o = block_scan(mine, lds, total) - mine;
+    int o = block_inclusive_scan<kWaves>(mine, lds, total) - mine;
     const int64_t block_off = reinterpret_cast<const int4 *>(a.workspace)[blockIdx.x].x;
 #pragma unroll
     for (int j = 0; j < kRows; ++j) {

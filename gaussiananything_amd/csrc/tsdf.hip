@@ -7,15 +7,19 @@
 // the structure does not: the hash map of 16^3-voxel units is a dense array of units over the object's bounding cube
 // (include/ga_tsdf.h), a frame is two launches (open units, integrate opened units: one workgroup per unit, one thread per
 // (x, y) column walking z exactly as Open3D's loop does, unit-blocked storage so that the 256 columns of a z-slice are one
-// contiguous kilobyte), and the mesh is four launches over the allocated units with device-side counts and offsets.
+// contiguous kilobyte), and the mesh is four launches over the allocated units with device-side counts and offsets (the scans inside a
+// unit are csrc/compact.h's, the one over the units is built on its wave scan).
 // HBM-bound streaming work: 20 B per voxel per frame for the opened units.  Compiled with -ffp-contract=off (the float
 // expressions are Open3D's, operation by operation).
 #include <hip/hip_runtime.h>
 
 #include "../../include/ga_tsdf.h"
+#include "compact.h"
 #include "mc_table.h"
 
 namespace ga {
+
+using namespace gacompact;
 
 constexpr int kUnitVox = GA_TSDF_UNIT * GA_TSDF_UNIT * GA_TSDF_UNIT;
 
@@ -188,24 +192,6 @@ __device__ __forceinline__ int vertex_flags(const VolP &vol, const MeshP &m, int
     return fx | (fy << 1) | (fz << 2);
 }
 
-// exclusive prefix of one int per thread over the 256 threads of the workgroup; `total` receives the sum
-__device__ __forceinline__ int block_exclusive(int v, int *sh4, int &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += o;
-    }
-    __syncthreads();
-    if (lane == 63) sh4[w] = inc;
-    __syncthreads();
-    int off = 0;
-    for (int k = 0; k < w; ++k) off += sh4[k];
-    total = sh4[0] + sh4[1] + sh4[2] + sh4[3];
-    return off + inc - v;
-}
-
 __global__ __launch_bounds__(256) void mc_count_kernel(VolP vol, MeshP m)
 {
     __shared__ int sh4[4];
@@ -226,11 +212,14 @@ __global__ __launch_bounds__(256) void mc_count_kernel(VolP vol, MeshP m)
         for (int k = 0; k < 16; ++k) m.vflags[base + k] = 0;
     }
     int tv, tt;
-    block_exclusive(nv, sh4, tv);
-    block_exclusive(nt, sh4, tt);
+    block_inclusive_scan<4>(nv, sh4, tv);
+    block_inclusive_scan<4>(nt, sh4, tt);
     if (threadIdx.x == 0) { m.unit_count[2 * u] = tv; m.unit_count[2 * u + 1] = tt; }
 }
 
+// Both columns of unit_count in one walk over the units, 64-bit (the totals are int64 in the interface).  The workgroup scan is written
+// out here: with sixteen 64-bit wave totals per column, block_inclusive_scan's unrolled loop took 86 VGPRs for the two columns (5 waves
+// per SIMD instead of 8), and one column after the other doubled the trips and the loads (profiles/compact_shared_header.txt)
 __global__ __launch_bounds__(1024) void mc_scan_units_kernel(MeshP m, int units, int64_t *counts)
 {
     __shared__ long long wave_tot[2][16];
@@ -243,11 +232,7 @@ __global__ __launch_bounds__(1024) void mc_scan_units_kernel(MeshP m, int units,
         long long v[2] = {0, 0}, inc[2];
         if (u < units) { v[0] = m.unit_count[2 * u]; v[1] = m.unit_count[2 * u + 1]; }
         for (int k = 0; k < 2; ++k) {
-            inc[k] = v[k];
-            for (int d = 1; d < 64; d <<= 1) {
-                const long long o = __shfl_up(inc[k], d, 64);
-                if (lane >= d) inc[k] += o;
-            }
+            inc[k] = wave_inclusive_scan(v[k]);
             if (lane == 63) wave_tot[k][w] = inc[k];
         }
         __syncthreads();
@@ -276,7 +261,7 @@ __global__ __launch_bounds__(256) void mc_vertices_kernel(VolP vol, MeshP m, flo
     int nv = 0;
     for (int k = 0; k < 16; ++k) nv += __popc(m.vflags[base + k]);
     int total;
-    int id = m.unit_base[2 * u] + block_exclusive(nv, sh4, total);
+    int id = m.unit_base[2 * u] + block_inclusive_scan<4>(nv, sh4, total) - nv;
     int ux, uy, uz;
     unit_coords(vol, u, ux, uy, uz);
     const int lx = threadIdx.x & 15, lz = threadIdx.x >> 4;
@@ -315,7 +300,7 @@ __global__ __launch_bounds__(256) void mc_triangles_kernel(VolP vol, MeshP m, in
     int nt = 0;
     for (int k = 0; k < 16; ++k) nt += kMcTriangleCount[m.cube[base + k]];
     int total;
-    int tri = m.unit_base[2 * u + 1] + block_exclusive(nt, sh4, total);
+    int tri = m.unit_base[2 * u + 1] + block_inclusive_scan<4>(nt, sh4, total) - nt;
     int ux, uy, uz;
     unit_coords(vol, u, ux, uy, uz);
     const int gx = ux * 16 + (threadIdx.x & 15), gz = uz * 16 + (threadIdx.x >> 4);

@@ -453,6 +453,38 @@ def _view_map(t, name, V, C, H, W, like, u8=False):
     return t.contiguous() if t.dtype == torch.uint8 else t.to(torch.float32).contiguous()
 
 
+def _check_views(depth, cameras, depth_kind, depth_range, mask_threshold, max_width=None):
+    """what ``unproject_depth_views`` and ``filter_view_consistency`` ask of their views, in this order -> (V, H, W, lo, hi, thr)"""
+    if not isinstance(depth, torch.Tensor) or depth.dim() not in (3, 4) or (depth.dim() == 4 and depth.shape[1] != 1) or depth.numel() == 0:
+        raise ValueError("depth is a [V, H, W] or [V, 1, H, W] tensor")
+    if not depth.is_floating_point():
+        raise TypeError("depth must be floating point")
+    V, H, W = int(depth.shape[0]), int(depth.shape[-2]), int(depth.shape[-1])
+    if max_width is None:
+        if V * H * W >= 2 ** 31:
+            raise ValueError("V * H * W stays below 2^31")
+    elif W > max_width or V * H * W >= 2 ** 31:
+        raise ValueError(f"views are at most {max_width} wide and V * H * W stays below 2^31")
+    if depth_kind not in _DEPTH_KINDS:
+        raise ValueError("depth_kind is 'z' (camera z) or 'ray' (distance along the normalised ray)")
+    if not isinstance(cameras, torch.Tensor) or cameras.dim() != 2 or cameras.shape[0] != V or cameras.shape[1] not in (25, 21):
+        raise ValueError(f"cameras is a pose25 tensor [{V}, 25] or cameras_from_view's [{V}, 21]")
+    lo, hi = (float(x) for x in depth_range)
+    if lo != lo or hi != hi or not lo < hi:
+        raise ValueError("depth_range is (min, max) with min < max")
+    thr = float(mask_threshold)
+    if thr != thr:
+        raise ValueError("mask_threshold must not be NaN")
+    return V, H, W, lo, hi, thr
+
+
+def _views_f32(depth, cameras):
+    """checked views, once their devices are known to be right -> the depth and the [V,21] cameras the kernels read: fp32, contiguous"""
+    from . import cameras as _cameras
+    cam = (_cameras.cameras_from_pose25(cameras) if cameras.shape[1] == 25 else cameras.detach().to(torch.float32)).contiguous()
+    return depth.detach().to(torch.float32).contiguous(), cam
+
+
 def unproject_candidates(V: int, H: int, W: int, pixel_stride: int = 1) -> int:
     """the pixels ``unproject_depth_views`` looks at: those with ``y % pixel_stride == 0 and x % pixel_stride == 0``"""
     s = int(pixel_stride)
@@ -474,23 +506,7 @@ def unproject_depth_views(depth: torch.Tensor, cameras: torch.Tensor, *, mask=No
     ``+-clip`` and with ``drop_zero`` none is exactly 0; ``pixel_stride`` s looks at every s-th row and column only.  ``capacity``
     (None: every candidate pixel) is the number of rows allocated; more valid pixels than that are reported by ``count`` alone.
     The arithmetic is the header's, operation by operation; GPU only, no fallback."""
-    if not isinstance(depth, torch.Tensor) or depth.dim() not in (3, 4) or (depth.dim() == 4 and depth.shape[1] != 1) or depth.numel() == 0:
-        raise ValueError("depth is a [V, H, W] or [V, 1, H, W] tensor")
-    if not depth.is_floating_point():
-        raise TypeError("depth must be floating point")
-    V, H, W = int(depth.shape[0]), int(depth.shape[-2]), int(depth.shape[-1])
-    if W > _lib.GA_PC_UNPROJECT_MAX_WIDTH or V * H * W >= 2 ** 31:
-        raise ValueError(f"views are at most {_lib.GA_PC_UNPROJECT_MAX_WIDTH} wide and V * H * W stays below 2^31")
-    if depth_kind not in _DEPTH_KINDS:
-        raise ValueError("depth_kind is 'z' (camera z) or 'ray' (distance along the normalised ray)")
-    if not isinstance(cameras, torch.Tensor) or cameras.dim() != 2 or cameras.shape[0] != V or cameras.shape[1] not in (25, 21):
-        raise ValueError(f"cameras is a pose25 tensor [{V}, 25] or cameras_from_view's [{V}, 21]")
-    lo, hi = (float(x) for x in depth_range)
-    if lo != lo or hi != hi or not lo < hi:
-        raise ValueError("depth_range is (min, max) with min < max")
-    thr = float(mask_threshold)
-    if thr != thr:
-        raise ValueError("mask_threshold must not be NaN")
+    V, H, W, lo, hi, thr = _check_views(depth, cameras, depth_kind, depth_range, mask_threshold, _lib.GA_PC_UNPROJECT_MAX_WIDTH)
     erode, stride = int(erode), int(pixel_stride)
     if not 0 <= erode <= _lib.GA_PC_UNPROJECT_MAX_ERODE:
         raise ValueError(f"erode must lie in [0, {_lib.GA_PC_UNPROJECT_MAX_ERODE}]")
@@ -512,9 +528,7 @@ def unproject_depth_views(depth: torch.Tensor, cameras: torch.Tensor, *, mask=No
     dev = depth.device
     if cameras.device != dev:
         raise RuntimeError(f"cameras must be on the depth's device {dev} (no CPU fallback)")
-    from . import cameras as _cameras
-    cam = (_cameras.cameras_from_pose25(cameras) if cameras.shape[1] == 25 else cameras.detach().to(torch.float32)).contiguous()
-    d = depth.detach().to(torch.float32).contiguous()
+    d, cam = _views_f32(depth, cameras)
     L = _lib.lib()
     with torch.cuda.device(dev):
         points = torch.empty(cap, 3, dtype=torch.float32, device=dev)
@@ -620,23 +634,7 @@ def filter_view_consistency(cloud, depth: torch.Tensor, cameras: torch.Tensor, *
     their order.  ``capacity`` (None: the input's rows) is the number of rows allocated.  ``return_votes`` adds the per-input-row
     ``support`` and ``conflicts`` (uint8, saturated).  The arithmetic is the header's, operation by operation; GPU only, no fallback."""
     what = "filter_view_consistency"
-    if not isinstance(depth, torch.Tensor) or depth.dim() not in (3, 4) or (depth.dim() == 4 and depth.shape[1] != 1) or depth.numel() == 0:
-        raise ValueError("depth is a [V, H, W] or [V, 1, H, W] tensor")
-    if not depth.is_floating_point():
-        raise TypeError("depth must be floating point")
-    V, H, W = int(depth.shape[0]), int(depth.shape[-2]), int(depth.shape[-1])
-    if V * H * W >= 2 ** 31:
-        raise ValueError("V * H * W stays below 2^31")
-    if depth_kind not in _DEPTH_KINDS:
-        raise ValueError("depth_kind is 'z' (camera z) or 'ray' (distance along the normalised ray)")
-    if not isinstance(cameras, torch.Tensor) or cameras.dim() != 2 or cameras.shape[0] != V or cameras.shape[1] not in (25, 21):
-        raise ValueError(f"cameras is a pose25 tensor [{V}, 25] or cameras_from_view's [{V}, 21]")
-    lo, hi = (float(x) for x in depth_range)
-    if lo != lo or hi != hi or not lo < hi:
-        raise ValueError("depth_range is (min, max) with min < max")
-    thr = float(mask_threshold)
-    if thr != thr:
-        raise ValueError("mask_threshold must not be NaN")
+    V, H, W, lo, hi, thr = _check_views(depth, cameras, depth_kind, depth_range, mask_threshold)
     tol_abs, tol_rel = (float(x) for x in tolerance)
     if not (0.0 <= tol_abs < float("inf") and 0.0 <= tol_rel < float("inf")):
         raise ValueError("tolerance is (absolute, relative), both finite and not negative")
@@ -651,9 +649,7 @@ def filter_view_consistency(cloud, depth: torch.Tensor, cameras: torch.Tensor, *
     if depth.device != dev or cameras.device != dev:
         raise RuntimeError(f"depth and cameras must be on the cloud's device {dev} (no CPU fallback)")
     m = _view_map(mask, "mask", V, 1, H, W, depth) if mask is not None else None
-    from . import cameras as _cameras
-    cam = (_cameras.cameras_from_pose25(cameras) if cameras.shape[1] == 25 else cameras.detach().to(torch.float32)).contiguous()
-    d = depth.detach().to(torch.float32).contiguous()
+    d, cam = _views_f32(depth, cameras)
     L = _lib.lib()
     with torch.cuda.device(dev):
         o = _filter_outputs(cap, dev, colors, normals, source, V)

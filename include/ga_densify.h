@@ -6,7 +6,7 @@
  * Conventions as in ga_fit.h: device pointers unless marked host, caller owns every buffer, work is enqueued on `stream`, 0 or a
  * negative GA_ERR_* code is returned, nothing synchronises, allocates or reads back.  No workgroup of any kernel here waits for
  * another one: the scan behind ga_densify is three launches (per-block sums, one workgroup scanning the sums, per-block rescan and
- * scatter), ordered by the stream alone.
+ * scatter), ordered by the stream alone; their shared pieces are csrc/compact.h.
  *
  * ARITHMETIC CONTRACT.  fp32, every product, quotient, sum and square root rounded on its own, in the order written (the translation
  * unit is built without FMA contraction; division and square root are the correctly rounded ones).  (float) of an int32 is the

@@ -44,7 +44,7 @@ extern "C" {
 #define GA_MESH_RECORD_FLOATS 16
 
 /* ---- surface sampling ------------------------------------------------------------------------------------------------------------
- * Three launches, shaped like ga_pc_unproject's:
+ * Three launches ordered by the stream, the form of csrc/compact.h (whose integer scans are not used: these sums are float64):
  *   1 area    workgroup g owns faces 256 g .. 256 g + 255, one per lane: w as above, widened to float64.  ONE lane then adds them in
  *             face order,  acc = 0.0;  acc = acc + w[j];  prefix[256 g + j] = acc   (float64, sequential), and the last acc is the
  *             block sum.  Sequential on purpose: a sum of non-negative terms taken in this order never decreases and stays EQUAL

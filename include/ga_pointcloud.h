@@ -280,7 +280,7 @@ int ga_pc_surfel_init(const GaSurfelInitArgs *args, void *stream);
  * (0, 0, 1) unless l > 0; source[r] = (v * H + y) * W + x.  Rows min(count, capacity) .. capacity - 1 hold zeros and source -1.
  * count[0] is the number of valid pixels even when it exceeds capacity (the only report of overflow), view_counts[v] that of view v.
  *
- * LAUNCHES: three, ordered by the stream, no workgroup waits for another, no atomics.  A workgroup owns a band of
+ * LAUNCHES: three, ordered by the stream, no workgroup waits for another, no atomics (scans and ranks: csrc/compact.h).  A workgroup owns a band of
  * rows_per_block = clamp(GA_PC_UNPROJECT_TILE_PIXELS / W, 1, H) full rows of one view, so workgroup order is source order.
  *     1 flag     validity of every pixel of the band (the thresholded mask staged in LDS with an erode-wide halo when erode > 0), one
  *                byte per pixel and the band's count to the workspace
@@ -347,7 +347,7 @@ int ga_pc_unproject(const GaUnprojectArgs *args, void *stream);
  * (optional, needs source) counts the kept rows, those beyond capacity included, by source / (H * W); a kept row whose source is
  * negative or names no view is counted nowhere.
  *
- * COMPACTION (both calls): a workgroup of GA_PC_FILTER_THREADS lanes owns a band of GA_PC_FILTER_BAND_ROWS consecutive rows.
+ * COMPACTION (both calls; scans and ranks: csrc/compact.h): a workgroup of GA_PC_FILTER_THREADS lanes owns a band of GA_PC_FILTER_BAND_ROWS consecutive rows.
  *     flag     one flag byte per row and the band's count to the workspace (the filter's flag pass is its voting kernel)
  *     scan     ONE workgroup walks the band counts GA_PC_FILTER_THREADS at a time with a register carry, leaves exclusive offsets and
  *              count, and zeroes view_counts
