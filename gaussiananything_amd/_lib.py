@@ -177,6 +177,27 @@ class GaVoxelThinArgs(ctypes.Structure):
                [("workspace_bytes", ctypes.c_size_t)]
 
 
+class GaAlignArgs(ctypes.Structure):
+    """include/ga_pointcloud.h: GaAlignArgs"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("batch", "num_points", "estimate_scale", "reserved")] + \
+               [(n, ctypes.c_void_p) for n in ("x", "y", "weights", "lengths", "transform", "rmse", "status", "workspace")] + \
+               [("workspace_bytes", ctypes.c_size_t)]
+
+
+class GaIcpArgs(ctypes.Structure):
+    """include/ga_pointcloud.h: GaIcpArgs"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("batch", "num_points", "num_target", "max_iterations", "estimate_scale", "reserved")] + \
+               [("relative_rmse_thr", ctypes.c_float), ("max_distance", ctypes.c_float)] + \
+               [(n, ctypes.c_void_p) for n in ("x", "y", "weights", "x_lengths", "y_lengths", "init_transform", "transform", "rmse",
+                                               "status", "iterations", "history", "xt", "idx", "dist2", "workspace")] + \
+               [("workspace_bytes", ctypes.c_size_t)]
+
+
+class GaAlignPlan(ctypes.Structure):
+    """include/ga_pointcloud.h: GaAlignPlan"""
+    _fields_ = [(n, ctypes.c_int32) for n in ("threads", "tile", "grid_x", "solve_threads", "sweeps", "terms")]
+
+
 class GaMeshSampleArgs(ctypes.Structure):
     """include/ga_mesh.h: GaMeshSampleArgs"""
     _fields_ = [(n, ctypes.c_int32) for n in ("num_vertices", "num_faces", "num_samples", "reserved")] + [("seed", ctypes.c_uint64)] + \
@@ -310,6 +331,8 @@ GA_PC_UNPROJECT_THREADS, GA_PC_UNPROJECT_TILE_PIXELS, GA_PC_UNPROJECT_MAX_WIDTH,
 GA_PC_CAMERA_FLOATS = 21
 GA_PC_FILTER_THREADS, GA_PC_FILTER_BAND_ROWS, GA_PC_FILTER_MAX_ROWS = 256, 1024, 1 << 30
 GA_PC_VOXEL_FIRST, GA_PC_VOXEL_CENTER, GA_PC_VOXEL_MAX_INDEX, GA_PC_VOXEL_WAVE_MERGE = 0, 1, (1 << 20) - 1, 1
+GA_PC_ALIGN_SWEEPS, GA_PC_ALIGN_TERMS, GA_PC_TRANSFORM_FLOATS, GA_PC_ALIGN_HISTORY_FLOATS = 6, 19, 13, 14
+GA_PC_ALIGN_RUNNING, GA_PC_ALIGN_CONVERGED, GA_PC_ALIGN_DEGENERATE, GA_PC_ICP_MAX_ITERATIONS = 0, 1, 2, 10000
 GA_MESH_THREADS, GA_MESH_PHILOX_STREAM, GA_MESH_MAX_FACES, GA_MESH_MAX_ROWS = 256, 0x4853454D, 1 << 27, 1 << 29
 
 EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspace_layout2", "ga_surfel_forward", "ga_surfel_postprocess",
@@ -319,6 +342,7 @@ EXPORTS = ("ga_surfel_version", "ga_surfel_workspace_layout", "ga_surfel_workspa
            "ga_pc_knn", "ga_pc_knn_plan", "ga_pc_knn_backward", "ga_pc_normals", "ga_pc_normals_plan", "ga_pc_surfel_init",
            "ga_pc_unproject", "ga_pc_unproject_workspace_bytes",
            "ga_pc_filter_views", "ga_pc_filter_views_workspace_bytes", "ga_pc_voxel_thin", "ga_pc_voxel_thin_workspace_bytes",
+           "ga_pc_align_plan", "ga_pc_align_workspace_bytes", "ga_pc_align_points", "ga_pc_icp",
            "ga_mesh_sample_plan", "ga_mesh_sample", "ga_mesh_point_distance_plan", "ga_mesh_point_distance",
            "ga_photo_loss_plan", "ga_photo_loss_workspace_bytes", "ga_photo_loss_forward", "ga_photo_loss_backward",
            "ga_geo_loss_plan", "ga_geo_loss_workspace_bytes", "ga_geo_loss_forward", "ga_geo_loss_backward",
@@ -413,6 +437,14 @@ def lib():
         L.ga_pc_voxel_thin.argtypes = [ctypes.POINTER(GaVoxelThinArgs), ctypes.c_void_p]
         L.ga_pc_voxel_thin_workspace_bytes.restype = ctypes.c_size_t
         L.ga_pc_voxel_thin_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int64]
+        L.ga_pc_align_plan.restype = ctypes.c_int
+        L.ga_pc_align_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GaAlignPlan)]
+        L.ga_pc_align_workspace_bytes.restype = ctypes.c_size_t
+        L.ga_pc_align_workspace_bytes.argtypes = [ctypes.c_int32, ctypes.c_int32]
+        L.ga_pc_align_points.restype = ctypes.c_int
+        L.ga_pc_align_points.argtypes = [ctypes.POINTER(GaAlignArgs), ctypes.c_void_p]
+        L.ga_pc_icp.restype = ctypes.c_int
+        L.ga_pc_icp.argtypes = [ctypes.POINTER(GaIcpArgs), ctypes.c_void_p]
         L.ga_mesh_sample_plan.restype = ctypes.c_int
         L.ga_mesh_sample_plan.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(GaMeshSamplePlan)]
         L.ga_mesh_sample.restype = ctypes.c_int

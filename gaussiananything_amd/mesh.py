@@ -385,16 +385,30 @@ def point_mesh_distance(points, vertices, faces, *, differentiable: bool = False
 
 
 @torch.no_grad()
-def mesh_cloud_distance(vertices, faces, points, *, num_samples: int = 100000, threshold: Optional[float] = None, seed=0):
+def mesh_cloud_distance(vertices, faces, points, *, num_samples: int = 100000, threshold: Optional[float] = None, seed=0,
+                        align: Optional[str] = None, max_iterations: int = 100):
     """How far a mesh lies from a cloud -- this project's OWN definition (no reference code for it runs here: UNPINNED):
         accuracy      mean distance from ``num_samples`` surface samples of the mesh to their nearest cloud point (``nearest_points``)
         completeness  mean distance from the cloud's points to the mesh surface (``point_mesh_distance``)
     and, with ``threshold`` (a distance), precision = the share of samples within it, recall = the share of cloud points within it and
     fscore = their harmonic mean (0 when both are 0).  ``points`` [N,3].  Distances, not squared.  -> dict of 0-dim device tensors;
-    nothing is read back."""
-    from .pointcloud import nearest_points
+    nothing is read back.
+
+    ``align`` = "rigid" | "similarity" first registers the cloud to the mesh's surface samples (``pointcloud.iterative_closest_point``,
+    at most ``max_iterations`` iterations, without / with scale) and measures the registered cloud; the dict then also holds
+    ``transform`` (SimilarityTransform of one cloud: R [1,3,3], T [1,3], s [1]), ``converged`` [1] and ``points`` [N,3], the registered
+    cloud.  ICP finds the nearest local optimum: a cloud far from the mesh's frame needs a coarse pose first.  ``align=None`` (the
+    default) measures the cloud as given."""
+    from .pointcloud import iterative_closest_point, nearest_points
+    if align not in (None, "rigid", "similarity"):
+        raise ValueError('align is None, "rigid" or "similarity"')
     samples = sample_points_from_mesh(vertices, faces, num_samples, seed=seed)
     cloud = points.detach().to(torch.float32).contiguous()
+    extra = {}
+    if align is not None:
+        sol = iterative_closest_point(cloud[None], samples[None], max_iterations=max_iterations, estimate_scale=align == "similarity")
+        cloud = sol.Xt[0]
+        extra = {"transform": sol.RTs, "converged": sol.converged, "points": cloud}
     to_cloud = nearest_points(samples[None], cloud[None])[0][0].sqrt()
     to_mesh = point_mesh_distance(cloud, vertices, faces).dist2.sqrt()
     out = {"accuracy": to_cloud.mean(), "completeness": to_mesh.mean()}
@@ -402,4 +416,5 @@ def mesh_cloud_distance(vertices, faces, points, *, num_samples: int = 100000, t
         precision, recall = (to_cloud <= threshold).float().mean(), (to_mesh <= threshold).float().mean()
         both = precision + recall
         out.update(precision=precision, recall=recall, fscore=torch.where(both > 0, 2 * precision * recall / both.clamp(min=1e-30), both))
+    out.update(extra)
     return out

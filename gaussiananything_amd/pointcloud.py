@@ -735,3 +735,176 @@ def cloud_from_render(out: dict, cam_view: torch.Tensor, tanfov, *, batch_index:
     if "depth_kind" in kw:
         raise ValueError("render's depth is the camera z: depth_kind is not a choice here")
     return unproject_depth_views(pick(out["depth"], 4), cam.to(out["depth"].device), depth_kind="z", **maps, **kw)
+
+
+# ---- registration (include/ga_pointcloud.h, csrc/pc_align.hip) ----------------------------------------------------------------------------
+SimilarityTransform = collections.namedtuple("SimilarityTransform", "R T s")
+ICPSolution = collections.namedtuple("ICPSolution", "converged rmse Xt RTs t_history iterations idx dist2 history")
+
+
+def align_plan(num_points: int, num_target: int = 1) -> dict:
+    """What ``ga_pc_align_points`` and ``ga_pc_icp`` launch: {'threads', 'tile', 'grid_x', 'solve_threads', 'sweeps', 'terms'} (the
+    accumulate grid is grid_x by B, the solve grid B)."""
+    pl = _lib.GaAlignPlan()
+    _lib.check(_lib.lib().ga_pc_align_plan(int(num_points), int(num_target), ctypes.byref(pl)), "ga_pc_align_plan")
+    return {k: getattr(pl, k) for k in ("threads", "tile", "grid_x", "solve_threads", "sweeps", "terms")}
+
+
+def _device_lengths(lengths, B, N, device, name):
+    """an int tensor already on the device is taken as it is (no host read; the kernels clamp it), anything else as ``_lengths`` does"""
+    if isinstance(lengths, torch.Tensor) and lengths.device.type == "cuda":
+        if lengths.shape != (B,) or lengths.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"{name} is an int32 / int64 tensor of {B} entries")
+        return lengths.to(device=device, dtype=torch.int32).contiguous()
+    return _lengths(lengths, B, N, device, name)[0]
+
+
+def _pair_weights(weights, B, N, device):
+    if weights is None:
+        return None
+    if not isinstance(weights, torch.Tensor) or weights.shape != (B, N):
+        raise ValueError(f"weights is a [{B}, {N}] tensor")
+    return weights.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _no_reflection(allow_reflection, what):
+    if allow_reflection:
+        raise NotImplementedError(f"{what}: reflections are not built, only allow_reflection=False (Horn's method yields proper rotations)")
+
+
+def _unpack_transform(rts):
+    return SimilarityTransform(rts[:, 1:10].reshape(-1, 3, 3), rts[:, 10:13], rts[:, 0])
+
+
+def _pack_transform(t, B, device):
+    """SimilarityTransform (or any (R [B,3,3], T [B,3], s [B]) triple) or a packed [B,13] tensor -> [B,13] fp32 on the device"""
+    if isinstance(t, torch.Tensor):
+        if t.shape != (B, _lib.GA_PC_TRANSFORM_FLOATS):
+            raise ValueError(f"a packed transform is [{B}, {_lib.GA_PC_TRANSFORM_FLOATS}]: s, R row-major, T")
+        return t.detach().to(device=device, dtype=torch.float32).contiguous()
+    try:
+        R, T, s = t
+    except (TypeError, ValueError):
+        raise ValueError("a transform is a SimilarityTransform(R, T, s) or a packed [B, 13] tensor") from None
+    if not all(isinstance(v, torch.Tensor) for v in (R, T, s)) or R.shape != (B, 3, 3) or T.shape != (B, 3) or s.shape != (B,):
+        raise ValueError(f"a SimilarityTransform holds R [{B},3,3], T [{B},3] and s [{B}]")
+    f = lambda v: v.detach().to(device=device, dtype=torch.float32)
+    return torch.cat([f(s)[:, None], f(R).reshape(B, 9), f(T)], 1).contiguous()
+
+
+@torch.no_grad()
+def apply_similarity_transform(X: torch.Tensor, RTs) -> torch.Tensor:
+    """``s * X @ R + T`` for X [B,N,3] and a SimilarityTransform (or a packed [B,13] tensor), with the kernels' own fp32 expression,
+    ``((x_0 * R_0b + x_1 * R_1b) + x_2 * R_2b) * s + T_b`` and every operation rounded on its own: the result has the bits of the ``Xt``
+    that ``iterative_closest_point`` returns.  Plain torch on X's device; no gradient."""
+    if not isinstance(X, torch.Tensor) or X.dim() != 3 or X.shape[-1] != 3:
+        raise ValueError("X is a [B, N, 3] tensor")
+    x = X.detach().to(torch.float32)
+    t = _pack_transform(RTs, x.shape[0], x.device)
+    cols = []
+    for b in range(3):
+        a = x[:, :, 0] * t[:, None, 1 + b]
+        a = a + x[:, :, 1] * t[:, None, 4 + b]
+        a = a + x[:, :, 2] * t[:, None, 7 + b]
+        a = a * t[:, None, 0]
+        cols.append(a + t[:, None, 10 + b])
+    return torch.stack(cols, 2)
+
+
+@torch.no_grad()
+def corresponding_points_alignment(X: torch.Tensor, Y: torch.Tensor, weights=None, estimate_scale: bool = False,
+                                   allow_reflection: bool = False, eps: float = 1e-9, *, lengths=None, return_status: bool = False):
+    """-> SimilarityTransform(R [B,3,3], T [B,3], s [B]) with ``s * X @ R + T ~ Y`` in the weighted least-squares sense:
+    ``pytorch3d.ops.corresponding_points_alignment`` for [B,N,3] clouds whose rows correspond (``ga_pc_align_points``: fp64 sums in a
+    fixed order, Horn's quaternion method, the result rounded to fp32 -- a function of the inputs alone).  ``weights`` [B,N] >= 0;
+    ``lengths`` [B] for padded batches; ``allow_reflection=True`` is not built; ``eps`` is accepted and unused (nothing is divided by a
+    clamped weight sum: a cloud without positive weight, or without extent when the scale is wanted, is DEGENERATE and gets the
+    identity).  ``return_status=True`` -> (transform, rmse [B] of the pairs as given, status [B] int32: 0 solved, 2 degenerate).
+    Outputs carry no gradient: an input that requires grad is detached."""
+    _no_reflection(allow_reflection, "corresponding_points_alignment")
+    float(eps)
+    x, y = _cloud(X, "X"), _cloud(Y, "Y")
+    if x.shape != y.shape or x.device != y.device:
+        raise ValueError("X and Y need the same shape and device: row i of Y is the partner of row i of X")
+    B, N, _ = x.shape
+    dev = x.device
+    w = _pair_weights(weights, B, N, dev)
+    ln = _device_lengths(lengths, B, N, dev, "lengths")
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        rts = torch.empty(B, _lib.GA_PC_TRANSFORM_FLOATS, dtype=torch.float32, device=dev)
+        rmse = torch.empty(B, dtype=torch.float32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        nbytes = int(L.ga_pc_align_workspace_bytes(B, N))
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        args = _lib.GaAlignArgs(B, N, int(bool(estimate_scale)), 0, x.data_ptr(), y.data_ptr(), _ptr(w), _ptr(ln), rts.data_ptr(),
+                                rmse.data_ptr(), status.data_ptr(), workspace.data_ptr(), nbytes)
+        _lib.check(L.ga_pc_align_points(ctypes.byref(args), _stream(dev)), "ga_pc_align_points")
+    out = _unpack_transform(rts)
+    return (out, rmse, status) if return_status else out
+
+
+@torch.no_grad()
+def iterative_closest_point(X: torch.Tensor, Y: torch.Tensor, init_transform=None, max_iterations: int = 100,
+                            relative_rmse_thr: float = 1e-6, estimate_scale: bool = False, allow_reflection: bool = False,
+                            verbose: bool = False, *, x_lengths=None, y_lengths=None, weights=None, max_correspondence_distance=None,
+                            return_history: bool = False) -> ICPSolution:
+    """``pytorch3d.ops.iterative_closest_point`` for X [B,N,3] against Y [B,M,3]: -> ICPSolution(converged [B] bool, rmse [B], Xt [B,N,3],
+    RTs = SimilarityTransform, t_history, iterations [B] int32, idx [B,N] int64, dist2 [B,N], history), all on the device.  ONE enqueue
+    (``ga_pc_icp``): ``max_iterations`` x (match + sum, solve) and a final match pass; convergence, freezing and the iteration count are
+    decided on the device, nothing is read back, and the call can be captured into a graph (with ``x_lengths`` / ``y_lengths`` None or
+    int tensors already on the device).  ``verbose=True`` is the only thing that reads back, after the call.
+
+    ``weights`` [B,N] >= 0 weigh the points of X; ``max_correspondence_distance`` drops the pairs farther apart than it from every
+    solve and from the rmse (the only robust device built).  ``return_history`` -> ``t_history``, the list of the ``max_iterations + 1``
+    transforms the passes ran under (pytorch3d's field), and ``history`` [B, max_iterations + 1, 14], the packed tensor its entries
+    view: s, R row-major, T and the rmse of the pass; the rows behind a frozen cloud's last pass repeat that pass.
+    Two deliberate differences from pytorch3d (include/ga_pointcloud.h): the rmse is the match pass's own (Open3D's definition), and
+    the transform is always solved from the original X, so stable matches converge for any threshold >= 0.
+    ``converged`` is False for a cloud that hit ``max_iterations`` and for a DEGENERATE one (no pair with positive weight, or no
+    extent when the scale is wanted), which keeps the transform it had.  ``allow_reflection=True`` is not built.  Outputs carry no
+    gradient: an input that requires grad is detached."""
+    _no_reflection(allow_reflection, "iterative_closest_point")
+    max_iterations = int(max_iterations)
+    if max_iterations < 0 or max_iterations > _lib.GA_PC_ICP_MAX_ITERATIONS:
+        raise ValueError(f"max_iterations must lie in [0, {_lib.GA_PC_ICP_MAX_ITERATIONS}]")
+    thr = float(relative_rmse_thr)
+    if not (0.0 <= thr < float("inf")):
+        raise ValueError("relative_rmse_thr is a finite number >= 0")
+    gate = 0.0 if max_correspondence_distance is None else float(max_correspondence_distance)
+    if max_correspondence_distance is not None and not (0.0 < gate < float("inf")):
+        raise ValueError("max_correspondence_distance is a positive finite distance (or None)")
+    x, y = _cloud(X, "X"), _cloud(Y, "Y")
+    if x.shape[0] != y.shape[0] or x.device != y.device:
+        raise ValueError("X and Y need the same batch size and device")
+    B, N, _ = x.shape
+    M = y.shape[1]
+    dev = x.device
+    w = _pair_weights(weights, B, N, dev)
+    xl = _device_lengths(x_lengths, B, N, dev, "x_lengths")
+    yl = _device_lengths(y_lengths, B, M, dev, "y_lengths")
+    init = _pack_transform(init_transform, B, dev) if init_transform is not None else None
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        rts = torch.empty(B, _lib.GA_PC_TRANSFORM_FLOATS, dtype=torch.float32, device=dev)
+        rmse = torch.empty(B, dtype=torch.float32, device=dev)
+        status = torch.empty(B, dtype=torch.int32, device=dev)
+        iterations = torch.empty(B, dtype=torch.int32, device=dev)
+        history = torch.empty(B, max_iterations + 1, _lib.GA_PC_ALIGN_HISTORY_FLOATS, dtype=torch.float32, device=dev) \
+            if return_history else None
+        xt = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+        idx = torch.empty(B, N, dtype=torch.int32, device=dev)
+        dist2 = torch.empty(B, N, dtype=torch.float32, device=dev)
+        nbytes = int(L.ga_pc_align_workspace_bytes(B, N))
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        args = _lib.GaIcpArgs(B, N, M, max_iterations, int(bool(estimate_scale)), 0, thr, gate, x.data_ptr(), y.data_ptr(), _ptr(w),
+                              _ptr(xl), _ptr(yl), _ptr(init), rts.data_ptr(), rmse.data_ptr(), status.data_ptr(), iterations.data_ptr(),
+                              _ptr(history), xt.data_ptr(), idx.data_ptr(), dist2.data_ptr(), workspace.data_ptr(), nbytes)
+        _lib.check(L.ga_pc_icp(ctypes.byref(args), _stream(dev)), "ga_pc_icp")
+    t_history = [_unpack_transform(history[:, k, :_lib.GA_PC_TRANSFORM_FLOATS]) for k in range(max_iterations + 1)] \
+        if return_history else None
+    sol = ICPSolution(status == _lib.GA_PC_ALIGN_CONVERGED, rmse, xt, _unpack_transform(rts), t_history, iterations, idx.long(), dist2, history)
+    if verbose:   # the one host read, after everything has been enqueued
+        for b, (c, it, r) in enumerate(zip(sol.converged.tolist(), iterations.tolist(), rmse.tolist())):
+            print(f"ICP cloud {b}: {'converged' if c else 'not converged'} after {it} iterations, rmse {r:.6e}")
+    return sol

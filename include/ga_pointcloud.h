@@ -473,6 +473,135 @@ size_t ga_pc_voxel_thin_workspace_bytes(int32_t rows, int64_t table_slots);
 int ga_pc_filter_views(const GaFilterViewsArgs *args, void *stream);
 int ga_pc_voxel_thin(const GaVoxelThinArgs *args, void *stream);
 
+/* ---- registration: Horn alignment of corresponding points and ICP (csrc/pc_align.hip) ----------------------------------------------------
+ * pytorch3d.ops.corresponding_points_alignment (Kabsch / Umeyama) and pytorch3d.ops.iterative_closest_point, restated from their
+ * published behaviour, parity UNPINNED.  tests/_align_ref.py reproduces every output bit for bit.
+ *
+ * TRANSFORM, pytorch3d's convention: Xt = s * X @ R + T, GA_PC_TRANSFORM_FLOATS = 13 fp32 per cloud: [0] s, [1..9] R row-major,
+ * [10..12] T.  The transformed point is fp32 with every operation rounded on its own:
+ *     xt_b = ((x_0 * R_0b + x_1 * R_1b) + x_2 * R_2b) * s + T_b                                            b = 0, 1, 2
+ *
+ * PAIRS.  Row i of X (i < its length) has one partner y: row i of Y (ga_pc_align_points), or the nearest row of Y to xt_i exactly as
+ * ga_pc_nearest finds it (ga_pc_icp: the dist2 contract above, the lowest index among equals).  d2 is dist2(x_i, y) of the contract for
+ * given pairs and dist2(xt_i, y) for matched ones.  The pair's weight is w = weights[b,i] (1 without weights; weights are >= 0, the
+ * caller's duty), 0 when a gate is given and d2 > gate2 (fp32 comparison, gate2 = max_distance * max_distance rounded to fp32), and a
+ * row past the length, or one with no target to match, contributes exact zeros.
+ *
+ * SUMS.  GA_PC_ALIGN_TERMS = 19 terms per pair, formed in fp64 from the fp32 values (the ORIGINAL x, never xt):
+ *     [0] w   [1..3] w * x_a   [4..6] w * y_a   [7 + 3a + b] (w * x_a) * y_b   [16] w * ((x_0 * x_0 + x_1 * x_1) + x_2 * x_2)
+ *     [17] w * ((y_0 * y_0 + y_1 * y_1) + y_2 * y_2)   [18] w * d2
+ * A workgroup of 256 consecutive rows sums each term as the balanced tree over the lane index, v[i] += v[i xor 2^l] for l = 0 .. 7, and
+ * the workgroups' sums are added in ascending order starting from the first.  No atomics: the sums are a function of the inputs alone.
+ *
+ * SOLVE, fp64 with only + - * / sqrt, |.| and comparisons.  W = S[0]; x_a = S[1 + a] / W; y_b = S[4 + b] / W;
+ *     M_ab = S[7 + 3a + b] / W - x_a * y_b;   vx = S[16] / W - ((x_0 * x_0 + x_1 * x_1) + x_2 * x_2);   rmse = sqrt(S[18] / W)
+ * Rotation by Horn's quaternion method (B. K. P. Horn, JOSA A 4(4), 1987).  The symmetric matrix
+ *     A_00 = (M_00 + M_11) + M_22   A_11 = (M_00 - M_11) - M_22   A_22 = (M_11 - M_00) - M_22   A_33 = (M_22 - M_00) - M_11
+ *     A_01 = M_12 - M_21   A_02 = M_20 - M_02   A_03 = M_01 - M_10   A_12 = M_01 + M_10   A_13 = M_20 + M_02   A_23 = M_12 + M_21
+ * is diagonalised by cyclic Jacobi: V = I, then GA_PC_ALIGN_SWEEPS sweeps of the rotations (p,q) = (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
+ * with the formulas of ga_pc_normals above (theta, t, c, s, h; both other rows r ascending; V_kp, V_kq for k = 0 .. 3), a rotation
+ * skipped only when A_pq is exactly 0, no data-dependent exit.  The quaternion is the column of V under the largest diagonal entry (the
+ * lowest column among equals), q / sqrt(((q_0 * q_0 + q_1 * q_1) + q_2 * q_2) + q_3 * q_3) = (w, x, y, z), and
+ *     R_00 = 1 - 2 * (yy + zz)   R_01 = 2 * (xy + wz)       R_02 = 2 * (xz - wy)
+ *     R_10 = 2 * (xy - wz)       R_11 = 1 - 2 * (xx + zz)   R_12 = 2 * (yz + wx)
+ *     R_20 = 2 * (xz + wy)       R_21 = 2 * (yz - wx)       R_22 = 1 - 2 * (xx + yy)          xx = x * x, xy = x * y, wz = w * z, ...
+ * always a proper rotation: pytorch3d's allow_reflection=False.  With estimate_scale s = (+0 + R_00 * M_00 + R_01 * M_01 + ... + R_22 *
+ * M_22) / vx (row-major order), otherwise s = 1;  T_b = y_b - s * ((x_0 * R_0b + x_1 * R_1b) + x_2 * R_2b).  s, R, T are rounded to fp32.
+ * When !(W > 0) the rmse is 0, and then or when the scale is wanted and !(vx > (S[16] / W) * 2^-40) -- no extent: the rounding of the
+ * sums leaves a coincident cloud a vx of about 1e-16 of its mean |x|^2, of either sign, so the test is not against 0 -- the
+ * transform stays as it was (the identity for ga_pc_align_points) and the cloud's status becomes GA_PC_ALIGN_DEGENERATE.
+ *
+ * Jacobi sweeps of the solve.  The restatement (tests/_align_ref.py) on the 152 weighted problems of tests/test_align_cpu.py (3 .. 200
+ * points, noise 0 .. 0.3, the planar and collinear ones included): the float64 transform still moves by 4e-3 from 3 sweeps to 4 and by
+ * 2.7e-10 from 4 to 5, and not in a single bit from 5 to 6 or beyond (the fp32 outputs already agree from 4 on).  5 is the smallest
+ * count whose result no longer changes; one more. */
+#define GA_PC_ALIGN_SWEEPS 6
+#define GA_PC_ALIGN_TERMS 19
+#define GA_PC_TRANSFORM_FLOATS 13
+#define GA_PC_ALIGN_HISTORY_FLOATS 14 /* a transform and the rmse of the pass that ran under it */
+#define GA_PC_ALIGN_RUNNING 0         /* ga_pc_align_points: solved; ga_pc_icp: max_iterations reached without convergence */
+#define GA_PC_ALIGN_CONVERGED 1
+#define GA_PC_ALIGN_DEGENERATE 2
+#define GA_PC_ICP_MAX_ITERATIONS 10000
+
+typedef struct GaAlignArgs {
+    int32_t batch;            /* B, 1 .. GA_PC_MAX_BATCH                                                   */
+    int32_t num_points;       /* N, N * 3 < 2^31                                                           */
+    int32_t estimate_scale;   /* 0 or 1                                                                    */
+    int32_t reserved;         /* 0                                                                         */
+    const float *x;           /* [B,N,3]                                                                   */
+    const float *y;           /* [B,N,3]: row i is the partner of row i of x                               */
+    const float *weights;     /* [B,N] or NULL (= 1)                                                       */
+    const int32_t *lengths;   /* [B] or NULL (= all N), clamped by the kernel                              */
+    float *transform;         /* [B,GA_PC_TRANSFORM_FLOATS]                                                */
+    float *rmse;              /* [B]: of the pairs as given, BEFORE the alignment                          */
+    int32_t *status;          /* [B]: GA_PC_ALIGN_RUNNING (solved) or GA_PC_ALIGN_DEGENERATE               */
+    void *workspace;          /* ga_pc_align_workspace_bytes(B, N) bytes, 16-byte aligned                  */
+    size_t workspace_bytes;
+} GaAlignArgs;
+
+/* ICP in one enqueue: pass k = 0 .. max_iterations matches under transform k and sums (one launch), then a solve launch of one small
+ * workgroup per cloud.  rmse_k is measured BY match pass k under transform k.  Solve k of a running cloud, in this order: writes rmse and
+ * history row k (transform k, rmse_k);  !(W > 0) -> DEGENERATE;  k >= 1 and |rmse_(k-1) - rmse_k| <= thr * rmse_(k-1) (fp64, thr the
+ * fp32 value widened) -> CONVERGED, decided BEFORE the update, so the transform stays the one whose matches gave rmse_k;  the final pass
+ * k = max_iterations stops here;  scale wanted and no extent (above) -> DEGENERATE;  otherwise transform k+1 is solved from the ORIGINAL x and
+ * the matches, and iterations[b] += 1.  A CONVERGED or DEGENERATE cloud is frozen: its match workgroups leave after one read of its
+ * status, its solves return, iterations[b] stops.  The final pass matches EVERY cloud once more and writes xt, idx and dist2 (padding as
+ * ga_pc_nearest: index -1, distance 0, point 0); for a frozen cloud it repeats history row iterations[b] in the rows behind it, so
+ * rmse[b] == history[b, iterations[b], 13] always.  Nothing is read back: the call can be captured into a graph.
+ *
+ * Two deliberate differences from pytorch3d.ops.iterative_closest_point:
+ *   rmse         pytorch3d measures it after the update, on the old matches.  Ours is the match pass's own sum of w * d2 -- no second
+ *                pass over the points, no cancellation: Open3D's definition.
+ *   convergence  the transform is always estimated from the original X, so stable matches give a bit-identical transform, the next
+ *                rmse is bit-identical, and convergence follows for any thr >= 0 (thr = 0 included). */
+typedef struct GaIcpArgs {
+    int32_t batch;               /* B, 1 .. GA_PC_MAX_BATCH                                                */
+    int32_t num_points;          /* N, rows of x, N * 3 < 2^31                                             */
+    int32_t num_target;          /* Nt, rows of y, Nt * 3 < 2^31                                           */
+    int32_t max_iterations;      /* 0 .. GA_PC_ICP_MAX_ITERATIONS                                          */
+    int32_t estimate_scale;      /* 0 or 1                                                                 */
+    int32_t reserved;            /* 0                                                                      */
+    float relative_rmse_thr;     /* >= 0, finite                                                           */
+    float max_distance;          /* the gate: 0 = none, else positive and finite                           */
+    const float *x;              /* [B,N,3]                                                                */
+    const float *y;              /* [B,Nt,3]                                                               */
+    const float *weights;        /* [B,N] or NULL (= 1)                                                    */
+    const int32_t *x_lengths;    /* [B] or NULL (= all N), clamped by the kernel                           */
+    const int32_t *y_lengths;    /* [B] or NULL (= all Nt), clamped by the kernel                          */
+    const float *init_transform; /* [B,GA_PC_TRANSFORM_FLOATS] or NULL (= identity); not `transform`       */
+    float *transform;            /* [B,GA_PC_TRANSFORM_FLOATS]                                             */
+    float *rmse;                 /* [B]                                                                    */
+    int32_t *status;             /* [B]: GA_PC_ALIGN_*                                                     */
+    int32_t *iterations;         /* [B]: the number of transform updates                                   */
+    float *history;              /* [B, max_iterations + 1, GA_PC_ALIGN_HISTORY_FLOATS] or NULL            */
+    float *xt;                   /* [B,N,3]: x under the returned transform                                */
+    int32_t *idx;                /* [B,N]: ga_pc_nearest of xt against y                                   */
+    float *dist2;                /* [B,N]                                                                  */
+    void *workspace;             /* ga_pc_align_workspace_bytes(B, N) bytes, 16-byte aligned               */
+    size_t workspace_bytes;
+} GaIcpArgs;
+
+/* what both calls launch: the accumulate grid (grid_x, B) of `threads` lanes, one lane per row of x, the targets staged in LDS tiles of
+ * `tile` points; the solve grid B workgroups of `solve_threads` lanes */
+typedef struct GaAlignPlan {
+    int32_t threads;
+    int32_t tile;
+    int32_t grid_x;        /* ceil(N / threads): the partial rows per cloud   */
+    int32_t solve_threads;
+    int32_t sweeps;        /* GA_PC_ALIGN_SWEEPS                              */
+    int32_t terms;         /* GA_PC_ALIGN_TERMS                               */
+} GaAlignPlan;
+
+/* host only, no HIP call: GA_OK, GA_ERR_NULL_ARG or GA_ERR_BAD_SHAPE */
+int ga_pc_align_plan(int32_t num_points, int32_t num_target, GaAlignPlan *plan);
+/* host: bytes of workspace both calls need (the fp64 partial rows and the previous rmse), 0 for a shape they reject */
+size_t ga_pc_align_workspace_bytes(int32_t batch, int32_t num_points);
+/* GA_OK, GA_ERR_NULL_ARG, GA_ERR_BAD_SHAPE (batch, N, Nt, max_iterations), GA_ERR_BAD_FLAGS (estimate_scale, reserved, the threshold or
+ * the gate out of range), GA_ERR_WORKSPACE or GA_ERR_LAUNCH -- everything but the last before anything touches the device */
+int ga_pc_align_points(const GaAlignArgs *args, void *stream);
+int ga_pc_icp(const GaIcpArgs *args, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
